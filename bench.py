@@ -1,7 +1,7 @@
 """Benchmark: PPO train steps on PPO CartPole-v1 (MLP[64,64], n_steps=128, synthetic
 observation replay), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1 started plainly: bench.py starts the N ranks itself under torch.distributed.run,
     one process per GPU, before any GPU call; under an external
     `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` it runs as
@@ -10,12 +10,18 @@ observation replay), one process per GPU.
 A step = one PPO train_step: fused rollout of n_envs x 128 steps (+GAE) and 4 epochs x 4
 minibatches (shuffle, forward, clipped loss, backward, global-norm clip, Keras Adam; one
 persistent launch on one GPU, all-reduce of the gradient when N>1).
-`value` = the metric's 16-env workload (BASELINE metric "PPO 16-env"); the line's `c2`
-object = BASELINE configs[1] (256 envs per GPU). Weak scaling: every rank owns its envs;
---global-envs N splits N envs over the ranks instead (strong scaling). At N = 1 the same
-line also carries compact `c3` / `c4` / `c5` objects (BASELINE configs[2..4]: value, ms per
-step, dominant-kernel roofline, a few-second CPU-port baseline); --config c3|c4|c5|trpo|acer
-prints a full line for one of them. Rank 0 prints ONE JSON line.
+`value` = the metric's 16-env workload (BASELINE metric "PPO 16-env"). Weak scaling: every
+rank owns its envs; --global-envs N splits N envs over the ranks instead (strong scaling).
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the
+result line (`value`, `ms_per_step`, the workload's `config`). --dump-outputs DIR then writes
+what the last timed step left (parameters, optimizer state, rollout buffers) as
+DIR/<name>.npy, so two builds can be compared output for output (same arguments = same
+inputs). --full adds everything else to the line: the rollout / update split and the
+per-kernel rooflines (event-timed passes of their own), the `c2` object = BASELINE
+configs[1] (256 envs per GPU), the `dynamics` object, the CPU-port baseline and, at N = 1,
+compact `c3` / `c4` / `c5` objects (BASELINE configs[2..4]: value, ms per step,
+dominant-kernel roofline, a few-second CPU-port baseline). --config c3|c4|c5|trpo|acer
+prints a line for one of those workloads instead. Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -56,13 +62,23 @@ def parse():
     p.add_argument('--global-envs', type=int, default=0,
                    help='strong scaling: this many envs in all, split over the ranks (the '
                         'headline line then reports scaling "strong"; default: --n-envs per GPU)')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what the headline does not need: the rollout / update '
+                        'split and per-kernel rooflines, the c2 and dynamics objects, the '
+                        'compact C3 / C4 / C5 objects, the CPU-port baseline')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write what the last one left (parameters, '
+                        'optimizer state, rollout buffers) as DIR/<name>.npy, f32 / f64, at '
+                        'most 64 MB in all (a fixed seeded sample of larger arrays)')
     p.add_argument('--no-secondary', dest='secondary', action='store_false',
-                   help='skip the compact C3 / C4 / C5 objects of the default one-GPU line')
+                   help='--full: skip the compact C3 / C4 / C5 objects of the one-GPU line')
     p.add_argument('--no-c2', dest='c2', action='store_false',
-                   help='skip the secondary BASELINE configs[1] (256 envs per GPU) measurement')
+                   help='--full: skip the secondary BASELINE configs[1] (256 envs per GPU) '
+                        'measurement')
     p.add_argument('--no-dynamics', dest='dynamics', action='store_false',
-                   help='skip the `dynamics` object (the headline workload on the CartPole-v1 '
-                        'dynamics env: the step-loop rollout of an action-dependent env)')
+                   help='--full: skip the `dynamics` object (the headline workload on the '
+                        'CartPole-v1 dynamics env: the step-loop rollout of an '
+                        'action-dependent env)')
     p.add_argument('--n-steps', type=int, default=128)
     p.add_argument('--t-rec', type=int, default=4096)
     p.add_argument('--seed', type=int, default=55)
@@ -218,7 +234,7 @@ def _timed(fn, steps, warmup, world):
 def secondary_cpu_baseline(args, kind, seconds=None, compact=False):
     """Bounded CPU sample of the C3 / C4 / C5 / TRPO / ACER workload (oracle/cpu_cnn.py,
     oracle/cpu_td3.py, oracle/cpu_trpo.py; kind "port"). compact: the few-second samples of
-    the default line's c3 / c4 / c5 objects (C4: 16 steps per env instead of 128)."""
+    the --full line's c3 / c4 / c5 objects (C4: 16 steps per env instead of 128)."""
     seconds = args.cpu_baseline_seconds if seconds is None else seconds
     sys.path.insert(0, str(ROOT / 'oracle'))
     import numpy as np
@@ -615,7 +631,7 @@ def run_secondary(args, config, world, rank, device, steps, warmup, cpu_seconds,
     return line
 
 
-# the default one-GPU line's compact secondary objects: (config, steps, warmup, CPU seconds)
+# the one-GPU --full line's compact secondary objects: (config, steps, warmup, CPU seconds)
 SECONDARY = (('c3', 30, 5, 4.0), ('c4', 3, 1, 3.0), ('c5', 30, 5, 3.0))
 
 
@@ -650,9 +666,39 @@ def compact_secondaries(args, device):
     return out
 
 
-def bench_ppo(args, world, rank, device, n_envs, env='replay'):
-    """Time PPO train steps on n_envs CartPole envs per rank; returns the measurements and
-    the per-kernel roofline of this workload. env 'replay': the synthetic observation replay
+DUMP_BYTES_MAX = 64 * 2**20
+
+
+def dump_outputs(agent, out_dir):
+    """What a caller of the timed path holds after its last step, as <name>.npy (f32; f64
+    for elements wider than 4 bytes): the parameters and the optimizer state the update
+    left, and the rollout buffers it trained on. An array over its share of DUMP_BYTES_MAX
+    is written as a fixed seeded sample of its flattened elements."""
+    import numpy as np
+    opt = agent.model.optimizer
+    arrays = {'theta': agent.model.theta, 'adam_m': opt.m, 'adam_v': opt.v,
+              'adam_iterations': opt.iterations, 'obs': agent.b_obs, 'actions': agent.b_act,
+              'log_probs': agent.b_logp, 'values': agent.b_val, 'entropies': agent.b_ent,
+              'rewards': agent.b_rew, 'dones': agent.b_done, 'episode_returns': agent.b_epret,
+              'returns': agent.b_ret}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES_MAX // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+        if a.nbytes > share:
+            idx = np.random.default_rng(20240229).choice(a.size, share // a.itemsize,
+                                                         replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(out_dir / f'{name}.npy', a)
+
+
+def bench_ppo(args, world, rank, device, n_envs, env='replay', full=True, dump_dir=None):
+    """Time PPO train steps on n_envs CartPole envs per rank; returns the measurements and,
+    with `full`, the rollout / update split and the per-kernel roofline of this workload
+    (event-timed passes after the timed region). `dump_dir`: rank 0 writes dump_outputs()
+    there right after the timed region. env 'replay': the synthetic observation replay
     of the metric (the record stream ignores the actions, so the rollout runs its T policy
     forwards as one batched launch, `replay_rollout_kernel`); 'dynamics': CartPole-v1
     dynamics on the device (`CartPoleVecEnv`, f64 as gym), whose next observation depends on
@@ -673,7 +719,7 @@ def bench_ppo(args, world, rank, device, n_envs, env='replay'):
         envs = ReplayVecEnv('CartPole-v1', n_envs, device=device, record=record)
     model = create_model(envs, 'ppo', 'model', optimizer_kwargs=dict(learning_rate=7e-4),
                          seed=args.seed, device=device)
-    theta0 = model.theta.cpu().numpy().copy()
+    theta0 = model.theta.cpu().numpy().copy() if full else None
     agent = PPO(envs, model, n_steps=args.n_steps, seed=args.seed, quiet=True,
                 use_graph=not args.no_graph)
     if world > 1:
@@ -695,6 +741,21 @@ def bench_ppo(args, world, rank, device, n_envs, env='replay'):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if dump_dir and rank == 0:
+        dump_outputs(agent, dump_dir)
+    if world > 1:
+        elapsed = _max_over_ranks(elapsed, device)
+    out = {
+        'n_envs': n_envs,
+        'value': n_envs * args.n_steps * args.steps * world / elapsed,
+        'ms_per_step': elapsed / args.steps * 1e3,
+        'transport': transport, 'graph': bool(agent.use_graph and agent._graph is not None),
+        'graph_steps': getattr(agent, '_graph_S', 1) if agent._graph is not None else 0,
+        'update_mode': agent.update_mode, 'record': record, 'theta0': theta0, 'agent': agent,
+    }
+    if not full:
+        agent._drain_episode_stats()
+        return out
     # the rollout / update split: the same K steps again with HIP events between the
     # phases, outside the timed region (an event record costs ~3 us of stream time)
     events = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
@@ -707,24 +768,14 @@ def bench_ppo(args, world, rank, device, n_envs, env='replay'):
     for _ in range(3):
         for k, v in agent.timed_train_step().items():
             ktimes.setdefault(k, []).extend(v)
-    if world > 1:
-        elapsed = _max_over_ranks(elapsed, device)
     agent._drain_episode_stats()
     T = args.n_steps
     B = n_envs * T
     mb = B // agent.mini_batches
     K = agent.ppo_epochs * agent.n_mb
     flops_sample = 3 * mlp_fwd_flops()  # forward + backward per sample
-    out = {
-        'n_envs': n_envs,
-        'value': n_envs * T * args.steps * world / elapsed,
-        'ms_per_step': elapsed / args.steps * 1e3,
-        'rollout_ms': float(np.mean([e[0].elapsed_time(e[1]) for e in events])),
-        'update_ms': float(np.mean([e[1].elapsed_time(e[2]) for e in events])),
-        'transport': transport, 'graph': bool(agent.use_graph and agent._graph is not None),
-        'graph_steps': getattr(agent, '_graph_S', 1) if agent._graph is not None else 0,
-        'update_mode': agent.update_mode, 'record': record, 'theta0': theta0, 'agent': agent,
-    }
+    out['rollout_ms'] = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
+    out['update_ms'] = float(np.mean([e[1].elapsed_time(e[2]) for e in events]))
     roll_ms = float(np.mean(ktimes['rollout']))
     if env == 'dynamics':
         per = DYNAMICS_ROLLOUT_BYTES_PER_ENV_STEP
@@ -803,6 +854,9 @@ def main():
         from xagents_amd import _lib
         _lib._lib = _lib.load(args.lib)
     if args.config != 'c2':
+        if args.dump_outputs:
+            raise SystemExit('--dump-outputs writes the headline workload\'s outputs '
+                             '(--config c2)')
         return bench_offpolicy_and_cnn(args)
     import torch.distributed as dist
 
@@ -813,13 +867,17 @@ def main():
     if args.global_envs and args.global_envs % world:
         raise SystemExit(f'--global-envs {args.global_envs} is not divisible by {world} ranks')
     n_head = args.global_envs // world if args.global_envs else args.n_envs
-    head = bench_ppo(args, world, rank, device, n_head)
-    c2 = bench_ppo(args, world, rank, device, 256) if args.c2 and n_head != 256 else None
+    full = args.full
+    head = bench_ppo(args, world, rank, device, n_head, full=full, dump_dir=args.dump_outputs)
+    # everything below the headline is measured with --full only
+    c2 = bench_ppo(args, world, rank, device, 256) if full and args.c2 and n_head != 256 \
+        else None
     # the same 16-env PPO on the CartPole-v1 dynamics env: the sequential step-loop rollout a
     # real (action-dependent) device env runs, beside the replay headline
-    dyn = bench_ppo(args, world, rank, device, n_head, env='dynamics') if args.dynamics else None
+    dyn = bench_ppo(args, world, rank, device, n_head, env='dynamics') \
+        if full and args.dynamics else None
     # BASELINE configs[2..4] as compact objects of the same one-GPU line
-    sec = compact_secondaries(args, device) if world == 1 and args.secondary else {}
+    sec = compact_secondaries(args, device) if full and world == 1 and args.secondary else {}
 
     if rank == 0:
         def dominant(r):
@@ -864,13 +922,19 @@ def main():
                 'update': head['update_mode'],
                 'allreduce': head['transport'],
             },
-            'update_ms': round(head['update_ms'], 4),
-            'rollout_ms': round(head['rollout_ms'], 4),
             'env_steps_per_sec_per_gpu': round(head['value'] / world, 1),
-            'roofline': dominant(head),
-            'update_roofline': head['update_roofline'],
-            'rollout_roofline': head['rollout_roofline'],
+            'full': full,
         }
+        if full:
+            line.update({
+                'update_ms': round(head['update_ms'], 4),
+                'rollout_ms': round(head['rollout_ms'], 4),
+                'roofline': dominant(head),
+                'update_roofline': head['update_roofline'],
+                'rollout_roofline': head['rollout_roofline'],
+            })
+        if args.dump_outputs:
+            line['outputs'] = str(args.dump_outputs)
         if c2 is not None:
             line['c2'] = {
                 'workload': 'PPO CartPole-v1, 256 envs/GPU, MLP[64,64], n_steps=128, 4x4 '
@@ -900,7 +964,7 @@ def main():
                 'rollout_roofline': dyn['rollout_roofline'],
             }
         line.update(sec)
-        if world == 1 and args.cpu_baseline_seconds > 0:
+        if full and world == 1 and args.cpu_baseline_seconds > 0:
             line['cpu_baseline'] = cpu_baseline(args, head['record'], head['theta0'])
         else:
             line['cpu_baseline'] = None

@@ -16,6 +16,37 @@ def test_mlp_forward_flops_match_survey():
     assert bench.mlp_fwd_flops() == 9088  # F = 9,088 FLOP per sample
 
 
+def test_dump_outputs_writes_float_arrays_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as f32 (an int64 counter as f64); an array over its
+    share of the byte budget becomes a sample that is the same from call to call."""
+    from types import SimpleNamespace as NS
+
+    import bench
+    g = torch.Generator().manual_seed(3)
+    f = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    opt = NS(m=f(70), v=f(70), iterations=torch.tensor([48], dtype=torch.int64))
+    agent = NS(model=NS(theta=f(70), optimizer=opt), b_obs=f(4, 8, 4),
+               b_act=torch.randint(0, 2, (4, 8), dtype=torch.int32, generator=g),
+               b_logp=f(4, 8), b_val=f(4, 8), b_ent=f(4, 8), b_rew=f(4, 8), b_done=f(4, 9),
+               b_epret=f(4, 8), b_ret=f(4, 8))
+    bench.dump_outputs(agent, tmp_path / 'a')
+    files = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert len(files) == 13 and all(n.endswith('.npy') for n in files)
+    got = {n[:-4]: np.load(tmp_path / 'a' / n) for n in files}
+    assert got['adam_iterations'].dtype == np.float64 and got['adam_iterations'][0] == 48
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != 'adam_iterations')
+    np.testing.assert_array_equal(got['obs'], agent.b_obs.numpy())
+    np.testing.assert_array_equal(got['actions'], agent.b_act.numpy().astype(np.float32))
+    # 13 arrays x 64 B each: obs (512 B) is sampled down to 16 of its elements, in order
+    monkeypatch.setattr(bench, 'DUMP_BYTES_MAX', 13 * 64)
+    bench.dump_outputs(agent, tmp_path / 'b')
+    bench.dump_outputs(agent, tmp_path / 'c')
+    b, c = np.load(tmp_path / 'b' / 'obs.npy'), np.load(tmp_path / 'c' / 'obs.npy')
+    assert b.shape == (16,) and np.array_equal(b, c)
+    assert np.isin(b, agent.b_obs.numpy()).all()
+    assert sum(np.load(p).nbytes for p in (tmp_path / 'b').iterdir()) <= 13 * 64
+
+
 def test_cpu_trpo_port_runs():
     import cpu_trpo
     from xagents_amd.envs import record_transitions

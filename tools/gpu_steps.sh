@@ -10,9 +10,9 @@
 #   configs  tests/test_gpu_configs.py (C3 / C4 / C5 at full size)
 #   variants bench A/B of tools/diag_lib/libxa_*.so (tools/build_variant.py) vs the product build
 #   smoke    __graft_entry__.smoke()
-#   bench    the default bench line (with the CPU baseline)
-#   ab       bench lines without the CPU baseline: XCD-local vs spread persistent update
-#   prof     rocprofv3 --kernel-trace --stats of the default bench (no CPU baseline)
+#   bench    the whole bench line (bench.py --full: headline, c2, dynamics, c3 / c4 / c5, CPU baselines)
+#   ab       --full bench lines without the CPU baseline: XCD-local vs spread persistent update
+#   prof     rocprofv3 --kernel-trace --stats of the whole bench line (--full, no CPU baseline)
 #   pmc      FETCH_SIZE / WRITE_SIZE passes per shape (tools/gpurun_pmc_shapes.sh)
 #   c3 c4 c5 acer trpo   secondary bench lines
 #   pollab   persistent-update poll sleep variants: bench + C2 FETCH_SIZE
@@ -73,7 +73,7 @@ for step in "$@"; do
     td3dp) run_pytest td3dp 450 tests/test_gpu_dp.py -k td3 ;;
     statab)
       # episode statistics stored by the update launch vs the xa_copy_to_host launch
-      B="python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       run stat_on1 200 $B
       XA_STATS_IN_UPDATE=0 run stat_off1 200 $B
       run stat_on2 200 $B
@@ -81,7 +81,7 @@ for step in "$@"; do
       python tools/bench_brief.py gpurun_out/${T}_stat_*.out ;;
     fixab)
       # the fixed-shape 16-env update kernel (BF = 3) vs the generic one, interleaved
-      B="python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       run fix_on1 200 $B
       XA_PPO_FIXED_SHAPE=0 run fix_off1 200 $B
       run fix_on2 200 $B
@@ -92,7 +92,7 @@ for step in "$@"; do
       # replaced was A/B'd in r05ra-r05rr, profiles/r05r*_replay_rollout_ab.txt)
       run_pytest roll 200 tests/test_gpu_kernels.py -k rollout
       XA_LIB=tools/diag_lib/libxa_rstamp.so run rstamps 200 python tools/rollout_stamps.py 16 256
-      B="python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       run roll_on1 200 $B
       run roll_on2 200 $B
       python tools/bench_brief.py gpurun_out/${T}_roll_*.out ;;
@@ -163,7 +163,7 @@ for step in "$@"; do
     gsab)
       # train steps per graph replay (XA_GRAPH_STEPS) and events per statistics group
       # (XA_STATS_EVERY), interleaved bench lines (headline + C2, no secondaries)
-      B="python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary --no-dynamics"
+      B="python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary --no-dynamics"
       run gs1a 200 $B
       XA_GRAPH_STEPS=4 run gs4a 200 $B
       XA_STATS_EVERY=4 run se4a 200 $B
@@ -196,15 +196,15 @@ for step in "$@"; do
         --master-port 29518 bench.py --config c5 --gpus 2 --steps 20 --warmup 3 \
         --cpu-baseline-seconds 0 ;;
     smoke) run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python bench.py --steps 20 --warmup 5 ;;
+    bench) run bench 300 python bench.py --full --steps 20 --warmup 5 ;;
     ab)
-      run ab_local 200 python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0
-      XA_PPO_LOCAL=0 run ab_spread 200 python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0
-      run ab_local2 200 python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0
+      run ab_local 200 python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0
+      XA_PPO_LOCAL=0 run ab_spread 200 python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0
+      run ab_local2 200 python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0
       python tools/bench_brief.py gpurun_out/${T}_ab_*.out ;;
     prof)
       (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${T}_prof \
-        -o run --output-format csv -- python $R/bench.py --steps 20 --warmup 5 \
+        -o run --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 \
         --cpu-baseline-seconds 0 > $R/gpurun_out/${T}_prof_bench.json 2>&1) || exit $? ;;
     pmc)
       TAG=${T} timeout -k 10 600 bash tools/gpurun_pmc_shapes.sh > gpurun_out/${T}_pmc.log 2>&1 || exit $?
@@ -216,7 +216,7 @@ for step in "$@"; do
     variants)
       # A/B of the diagnostic variant libraries (tools/build_variant.py) against the product
       # build, interleaved: base, each variant, base again (bench lines without CPU baseline)
-      B="python bench.py --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 40 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       run var_base1 200 $B
       for L in tools/diag_lib/libxa_*.so; do
         n=$(basename $L .so); n=${n#libxa_}
@@ -275,7 +275,7 @@ for step in "$@"; do
       done ;;
     gs8ab)
       # PPO train steps per graph replay: XA_GRAPH_STEPS 8 (default) vs 4, interleaved
-      B="python bench.py --steps 20 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 20 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       for r in 1 2 3; do
         run gs8_$r 200 $B
         XA_GRAPH_STEPS=4 run gs4_$r 200 $B
@@ -297,7 +297,7 @@ for step in "$@"; do
       done ;;
     c2gs)
       # C2 train steps per graph replay: 8 (forced) vs the default (4 above 4096 env-steps)
-      B="python bench.py --n-envs 256 --no-c2 --steps 24 --warmup 5 --cpu-baseline-seconds 0 --no-secondary --no-dynamics"
+      B="python bench.py --full --n-envs 256 --no-c2 --steps 24 --warmup 5 --cpu-baseline-seconds 0 --no-secondary --no-dynamics"
       for r in 1 2; do
         XA_GRAPH_STEPS=8 run c2gs8_$r 200 $B
         run c2gs4_$r 200 $B
@@ -306,7 +306,7 @@ for step in "$@"; do
     c2g)
       # C2 update grid A/B: fewer workgroups with more tiles each (XA_PPO_MAX_BLOCKS)
       for G in ${C2_GS:-256 128}; do
-        XA_PPO_MAX_BLOCKS=$G run c2g_$G 200 python bench.py --steps 30 --warmup 5 \
+        XA_PPO_MAX_BLOCKS=$G run c2g_$G 200 python bench.py --full --steps 30 --warmup 5 \
           --cpu-baseline-seconds 0 --no-secondary
       done
       python tools/bench_brief.py gpurun_out/${T}_c2g_*.out ;;
@@ -334,7 +334,7 @@ for step in "$@"; do
       # poll-round sleep of the persistent update (XA_POLL_SLEEP variants,
       # tools/diag_lib/libxa_poll*.so) vs the product: bench lines (16-env + C2) and the
       # C2 update's FETCH_SIZE per launch
-      B="python bench.py --steps 30 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
+      B="python bench.py --full --steps 30 --warmup 5 --cpu-baseline-seconds 0 --no-secondary"
       run poll_base 200 $B
       for L in tools/diag_lib/libxa_poll*.so; do
         n=$(basename $L .so); n=${n#libxa_}
