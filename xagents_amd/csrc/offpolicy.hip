@@ -175,10 +175,11 @@ __global__ __launch_bounds__(256) void polyak_kernel(const float* __restrict__ x
 
 __global__ void step_bump_kernel(int* step) { step[0] += 1; }
 
-// dz = dy * act'(y) from the layer output y (relu: y > 0; tanh: 1 - y^2)
+// dz = dy * act'(y) from the layer output y (relu: y > 0; tanh: 1 - y^2); dz may be dy
+// (the layer executor's in-place calls), so that pair carries no __restrict__
 __global__ __launch_bounds__(256) void act_grad_kernel(const float* __restrict__ y,
-                                                       const float* __restrict__ dy, int64_t n,
-                                                       int act, float* __restrict__ dz) {
+                                                       const float* dy, int64_t n, int act,
+                                                       float* dz) {
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const float v = y[e];
     float d = dy[e];
