@@ -36,6 +36,8 @@ extern "C" {
 /* environment kinds for the fused rollout */
 #define XA_ENV_REPLAY 0   /* synthetic pre-recorded observation replay (BASELINE config 2) */
 #define XA_ENV_CARTPOLE 1 /* CartPole-v1 dynamics on device (gym classic_control semantics) */
+#define XA_ENV_ACROBOT 2  /* Acrobot-v1 dynamics on device (book variant, RK4, obs 6, 3 actions) */
+#define XA_ENV_MOUNTAINCAR 3 /* MountainCar-v0 dynamics on device (obs 2, 3 actions) */
 
 /* return kinds computed at the end of the fused rollout */
 #define XA_RETURNS_NONE 0
@@ -102,9 +104,10 @@ typedef struct XaRolloutArgs {
   int n_envs, n_steps, obs_dim, n_actions;
   const float* theta; /* flat actor-critic parameters */
 
-  int env_kind;           /* XA_ENV_REPLAY / XA_ENV_CARTPOLE */
+  int env_kind;           /* XA_ENV_* (the dynamics kinds fix obs_dim and n_actions) */
   float* env_state;       /* [N,obs] post-reset current observation (BaseAgent.states) */
-  double* env_state64;    /* [N,4]   CartPole internal f64 state (cartpole only) */
+  double* env_state64;    /* [N,4]   internal f64 state of the dynamics envs (MountainCar
+                             uses slots 0 and 1 and leaves the rest untouched) */
   float* env_done;        /* [N]     last done flags (BaseAgent.dones) */
   int* env_cursor;        /* [N]     replay position / elapsed episode steps */
   float* ep_return;       /* [N]     running episode return (BaseAgent.episode_rewards) */
@@ -113,7 +116,8 @@ typedef struct XaRolloutArgs {
   const float* rep_rew;   /* [N,t_rec] */
   const float* rep_done;  /* [N,t_rec] 0/1 */
   int t_rec;
-  int max_episode_steps;  /* CartPole TimeLimit (500 for v1) */
+  int max_episode_steps;  /* gym TimeLimit of the dynamics envs (CartPole-v1 500, Acrobot-v1
+                             500, MountainCar-v0 200) */
 
   const float* uniforms;  /* [N,T] or NULL */
   uint64_t seed;
@@ -774,6 +778,37 @@ typedef struct XaWalkerStepArgs {
 } XaWalkerStepArgs;
 
 int xa_walker_step(const XaWalkerStepArgs* args, void* stream);
+
+/* Acrobot-v1 / MountainCar-v0 on device, one env step per launch: gym's env.step / env.reset
+ * of BaseAgent.step_envs (xagents/base.py:388-426, gym call base.py:408) for the two ids, for
+ * agents that run their models on the layer executor (the fused rollout steps the same
+ * dynamics in-kernel, bit for bit: csrc/classic_envs.hpp). env_kind = XA_ENV_ACROBOT (obs 6)
+ * or XA_ENV_MOUNTAINCAR (obs 2), 3 actions each. state64 [n_envs][4] f64 and elapsed [n_envs]
+ * int (steps into the episode) are the env's own memory. A step reads env e's action at
+ * actions[e * act_ld] (clamped to [0, 3) on device; validating them is the caller's job),
+ * applies the TimeLimit max_episode_steps and writes the returned obs (pre-reset) to out_obs
+ * [n_envs][obs], reward and done, and the post-step obs (the reset obs when done) to out_post
+ * -- the one-step record xa_replay_env_step consumes. A finished env resets from Philox
+ * (env, t, *counter; seed), the draw the fused rollout makes at step t. reset_only = 1 resets
+ * every env into out_post. */
+typedef struct XaClassicStepArgs {
+  int env_kind, n_envs;
+  double* state64;
+  int* elapsed;
+  const int* actions;
+  int64_t act_ld;
+  uint64_t seed;
+  const uint64_t* counter; /* device u64 (NULL = 0), read-only here */
+  int t;
+  int max_episode_steps;
+  int reset_only;
+  float* out_obs;
+  float* out_post;
+  float* out_rew;
+  float* out_done;
+} XaClassicStepArgs;
+
+int xa_classic_step(const XaClassicStepArgs* args, void* stream);
 
 /* Episode statistics to the host (BaseAgent.step_envs bookkeeping, xagents/base.py:388-426):
  * copies n_segments device buffers (bytes a multiple of 4) into pinned host memory in ONE

@@ -6,8 +6,8 @@
 //
 // Two schedules. The replay env (records that ignore the actions) runs every step's
 // forward as an independent row of one batched forward (replay_rollout_kernel, below).
-// The CartPole-dynamics env, whose next input depends on the sampled action, runs the
-// step loop (mlp_rollout_kernel): ONE wave64 per env, lane j = hidden unit j. Each lane
+// The dynamics envs (CartPole-v1, Acrobot-v1, MountainCar-v0), whose next input depends on
+// the sampled action, run the step loop (mlp_rollout_kernel): ONE wave64 per env, lane j = hidden unit j. Each lane
 // keeps the weights it needs for the whole rollout in VGPRs (column j of W1 and W2, row j
 // of the heads: ~75 registers). Per step:
 //   h1_j = tanh(sum_k x_k W1[k][j] + b1_j)              (fma chain over k)
@@ -15,13 +15,14 @@
 //   h2_j = tanh(sum of 8 interleaved 8-long fma chains + b2_j)
 //   h2 -> the wave's LDS row of this step (a [64 steps][64 units] chunk buffer)
 //   logit_a = butterfly_sum_j(h2_j * W3[j][a]) + b3_a (the sample needs them)
-//   inverse-CDF sample, then the f64 CartPole dynamics
+//   inverse-CDF sample, then the env's f64 dynamics (RollEnv<kind>)
 // and once per 64-step chunk, lane j on step t0 + j: the value head from the step's h2
 // row, summed in the pairwise order of the wave butterfly (bitwise the same sums as
 // in-step); softmax, log-prob and entropy. Envs are independent, so no inter-wave
 // synchronisation exists anywhere.
 // The arithmetic order above is restated exactly by oracle/xa_oracle.c.
 #include "../../include/xagents_hip.h"
+#include "classic_envs.hpp"
 #include "xa_common.hpp"
 
 namespace {
@@ -309,6 +310,28 @@ XA_DEV bool cartpole_step(double (&s)[4], int action) {
   return s[0] < -2.4 || s[0] > 2.4 || s[2] < -theta_thr || s[2] > theta_thr;
 }
 
+// The dynamics envs of the step loop: step (gym's `terminated`; the loop adds the TimeLimit),
+// the step's reward, reset from the step's four reset uniforms, observation. Acrobot-v1 and
+// MountainCar-v0 are classic_envs.hpp's, shared with xa_classic_step.
+template <int KIND>
+struct RollEnv : XaClassicEnv<KIND> {};
+
+template <>
+struct RollEnv<XA_ENV_CARTPOLE> {
+  static constexpr int kObs = 4, kActions = 2;
+  static XA_DEV bool step(double (&s)[4], int action) { return cartpole_step(s, action); }
+  static XA_DEV float reward(bool) { return 1.0f; }
+  // np_random.uniform(-0.05, 0.05, size=(4,))
+  static XA_DEV void reset(double (&s)[4], const double (&u)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = -0.05 + 0.1 * u[k];
+  }
+  static XA_DEV void obs(const double (&s)[4], float (&o)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (float)s[k];
+  }
+};
+
 // The sampling uniforms of 64 consecutive steps, lane j holding step t0 + j, fetched a
 // chunk ahead and read back per step with readlane (no memory access on the step chain).
 struct StepChunk {
@@ -332,9 +355,11 @@ XA_DEV float xa_readlane(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
-// the CartPole-dynamics env (the next input depends on the sampled action)
-template <int OBS, int A>
+// the dynamics envs (the next input depends on the sampled action)
+template <int OBS, int A, int KIND>
 __global__ __launch_bounds__(64 * kRollWaves) void mlp_rollout_kernel(XaRolloutArgs p) {
+  using Env = RollEnv<KIND>;
+  static_assert(Env::kObs == OBS && Env::kActions == A, "env kind and network shape disagree");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int AH = A + 1, AHP = (AH + 3) & ~3;
   constexpr int HF = A;  // first head of the chunk pass: the value
@@ -406,10 +431,10 @@ __global__ __launch_bounds__(64 * kRollWaves) void mlp_rollout_kernel(XaRolloutA
         const float u = p.uniforms ? xa_readlane(c.u_given, j) : xa_readlane(c.u_philox, j);
         const int act = cat_sample<A>(logits, u);
         XA_STAMP(4);
-        bool done = cartpole_step(cp, act);
+        bool done = Env::step(cp, act);
+        r = Env::reward(done);
         cur = cur + 1;
         if (cur >= p.max_episode_steps) done = true;  // gym TimeLimit
-        r = 1.0f;
         d = done ? 1.0f : 0.0f;
         if (mine) {
 #pragma unroll
@@ -418,17 +443,11 @@ __global__ __launch_bounds__(64 * kRollWaves) void mlp_rollout_kernel(XaRolloutA
           b_rew = r;
           b_done = d;
         }
-#pragma unroll
-        for (int k = 0; k < OBS; ++k) x[k] = (float)cp[k < 4 ? k : 3];  // pre-reset obs
+        Env::obs(cp, x);  // pre-reset obs
         if (done) {
-          // reset: np_random.uniform(-0.05, 0.05, size=(4,))
-          const xa_u4 rr = xa_philox((uint32_t)env, (uint32_t)(t0 + j), (uint32_t)ctr,
-                                     (uint32_t)(ctr >> 32) ^ 0x5eed5eedu, (uint32_t)p.seed,
-                                     (uint32_t)(p.seed >> 32));
-          const uint32_t rv[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            cp[k] = -0.05 + 0.1 * ((double)rv[k] * 2.3283064365386963e-10);
+          double ur[4];
+          xa_reset_uniforms(env, t0 + j, ctr, p.seed, ur);
+          Env::reset(cp, ur);
           cur = 0;
         }
       }
@@ -454,10 +473,8 @@ __global__ __launch_bounds__(64 * kRollWaves) void mlp_rollout_kernel(XaRolloutA
     const CatOut<A> cat = categorical<A>(b_l, u, b_act);
     float o_obs[OBS];
 #pragma unroll
-    for (int k = 0; k < OBS; ++k) {
-      o_obs[k] = b_obs[k];
-      st[k] = (float)cp[k < 4 ? k : 3];  // post-reset state
-    }
+    for (int k = 0; k < OBS; ++k) o_obs[k] = b_obs[k];
+    Env::obs(cp, st);  // post-reset state
     XA_STAMP(7);
     if (lane < n) {
       const size_t o = (size_t)env * T + t0 + lane;
@@ -1103,8 +1120,16 @@ int launch_rollout(const XaRolloutArgs* p, hipStream_t s) {
   const size_t lds = (size_t)kRollWaves * H * sizeof(float) +
                      (fused ? (size_t)kRollWaves * 3 * p->n_steps * sizeof(float) : 0);
   dim3 grid((p->n_envs + kRollWaves - 1) / kRollWaves);
+  // xa_mlp_rollout has checked that the kind and the shape agree
   if constexpr (OBS == 4 && A == 2)
-    hipLaunchKernelGGL((mlp_rollout_kernel<OBS, A>), grid, dim3(64 * kRollWaves), lds, s, *p);
+    hipLaunchKernelGGL((mlp_rollout_kernel<OBS, A, XA_ENV_CARTPOLE>), grid,
+                       dim3(64 * kRollWaves), lds, s, *p);
+  else if constexpr (OBS == 6 && A == 3)
+    hipLaunchKernelGGL((mlp_rollout_kernel<OBS, A, XA_ENV_ACROBOT>), grid,
+                       dim3(64 * kRollWaves), lds, s, *p);
+  else if constexpr (OBS == 2 && A == 3)
+    hipLaunchKernelGGL((mlp_rollout_kernel<OBS, A, XA_ENV_MOUNTAINCAR>), grid,
+                       dim3(64 * kRollWaves), lds, s, *p);
   XA_CHECK_LAUNCH("xa_mlp_rollout");
   return 0;
 }
@@ -1140,6 +1165,15 @@ extern "C" int xa_mlp_rollout(const XaRolloutArgs* p, void* stream) {
     XA_CHECK_ARG(p->env_state64 && p->obs_dim == 4 && p->n_actions == 2 &&
                      p->max_episode_steps > 0,
                  "xa_mlp_rollout: cartpole env needs env_state64, obs_dim 4, 2 actions");
+  } else if (p->env_kind == XA_ENV_ACROBOT || p->env_kind == XA_ENV_MOUNTAINCAR) {
+    const bool acro = p->env_kind == XA_ENV_ACROBOT;
+    const char* name = acro ? "acrobot" : "mountaincar";
+    XA_CHECK_ARG(p->obs_dim == (acro ? 6 : 2) && p->n_actions == 3,
+                 "xa_mlp_rollout: %s env needs obs_dim %d and 3 actions, got (%d, %d)", name,
+                 acro ? 6 : 2, p->obs_dim, p->n_actions);
+    XA_CHECK_ARG(p->env_state64 != nullptr, "xa_mlp_rollout: %s env needs env_state64", name);
+    XA_CHECK_ARG(p->max_episode_steps > 0,
+                 "xa_mlp_rollout: %s env needs max_episode_steps > 0", name);
   } else {
     XA_CHECK_ARG(false, "xa_mlp_rollout: unknown env_kind %d", p->env_kind);
   }

@@ -10,14 +10,19 @@ all n envs lives in HBM and is stepped inside the fused rollout kernel:
   restatement with a seeded random policy; stepping advances a per-env cursor.
 * CartPoleVecEnv -- gym CartPole-v1 dynamics (Euler, f64 state, TimeLimit 500)
   evaluated on device, actions applied.
+* AcrobotVecEnv / MountainCarVecEnv -- gym Acrobot-v1 (book dynamics, RK4, TimeLimit 500)
+  and MountainCar-v0 (TimeLimit 200) in the same fused rollout; ClassicControlVecEnv steps
+  the same two dynamics one launch per env step (xa_classic_step) for the agents whose
+  models run on the layer executor.
 
-Both expose the gym-like surface the agents use: len(), observation_space.shape,
+All expose the gym-like surface the agents use: len(), observation_space.shape,
 action_space (Discrete/Box), seed(), reset().
 """
 import numpy as np
 import torch
 
-from xagents_amd._lib import XA_ENV_CARTPOLE, XA_ENV_REPLAY
+from xagents_amd._lib import (XA_ENV_ACROBOT, XA_ENV_CARTPOLE, XA_ENV_MOUNTAINCAR,
+                              XA_ENV_REPLAY)
 from xagents_amd.nets import default_device
 
 
@@ -226,6 +231,64 @@ class CartPoleVecEnv(DeviceVecEnv):
         a.max_episode_steps = self.max_episode_steps
 
 
+def classic_initial_state(kind, n_envs, rng):
+    """env.reset() of n_envs Acrobot-v1 / MountainCar-v0 envs from a numpy generator: the
+    f64 state [n, 4] (MountainCar: position, velocity = 0, two unused slots) and its f32
+    observation."""
+    s = np.zeros((n_envs, 4))
+    if kind == XA_ENV_ACROBOT:
+        s[:] = rng.uniform(-0.1, 0.1, (n_envs, 4))
+        obs = np.stack([np.cos(s[:, 0]), np.sin(s[:, 0]), np.cos(s[:, 1]), np.sin(s[:, 1]),
+                        s[:, 2], s[:, 3]], 1)
+    else:
+        s[:, 0] = rng.uniform(-0.6, -0.4, n_envs)
+        obs = s[:, :2]
+    return s, obs.astype(np.float32)
+
+
+class ClassicDynamicsVecEnv(DeviceVecEnv):
+    """Acrobot-v1 / MountainCar-v0 dynamics in the fused rollout (csrc/classic_envs.hpp):
+    f64 state [n, 4] on device, the policy sees its f32 observation; 3 actions."""
+
+    env_id = None
+    obs_dim_ = None
+    max_episode_steps = None
+
+    def __init__(self, n_envs=1, seed=None, device=None):
+        super().__init__(self.env_id, n_envs, (self.obs_dim_,), Discrete(3), device)
+        self.spec.max_episode_steps = self.max_episode_steps
+        self.state64 = torch.zeros(self.n_envs, 4, dtype=torch.float64, device=self.device)
+        self._seed = seed
+        self.reset()
+
+    def reset(self):
+        s, obs = classic_initial_state(self.kind, self.n_envs, np.random.default_rng(self._seed))
+        self.state64.copy_(torch.from_numpy(s))
+        self.state.copy_(torch.from_numpy(obs))
+        self.cursor.zero_()
+        self.done.zero_()
+        self.ep_return.zero_()
+        return self.state
+
+    def fill_rollout_args(self, a):
+        super().fill_rollout_args(a)
+        a.env_state64 = self.state64.data_ptr()
+        a.max_episode_steps = self.max_episode_steps
+
+
+class AcrobotVecEnv(ClassicDynamicsVecEnv):
+    kind = XA_ENV_ACROBOT
+    env_id, obs_dim_, max_episode_steps = 'Acrobot-v1', 6, 500
+
+
+class MountainCarVecEnv(ClassicDynamicsVecEnv):
+    kind = XA_ENV_MOUNTAINCAR
+    env_id, obs_dim_, max_episode_steps = 'MountainCar-v0', 2, 200
+
+
+CLASSIC_ENVS = {'Acrobot-v1': AcrobotVecEnv, 'MountainCar-v0': MountainCarVecEnv}
+
+
 def record_transitions(n_envs, t_rec, obs_shape, dtype, seed=55, mean_episode=200,
                        reward_prob=0.02):
     """Synthetic pre-recorded transition streams for the off-policy configs
@@ -376,13 +439,108 @@ class WalkerVecEnv(TransitionReplayVecEnv):
         call('xa_walker_step', ctypes.byref(a), stream())
 
 
-def create_envs(env_name, n=1, preprocess=False, *args, mode='replay', seed=55, device=None,
+class ClassicControlVecEnv(TransitionReplayVecEnv):
+    """Acrobot-v1 / MountainCar-v0 behind the executor env step (csrc/classic_envs.hip): the
+    dynamics of AcrobotVecEnv / MountainCarVecEnv, bit for bit, one xa_classic_step launch
+    per env step (pre_step, given the step's actions) into the one-step record that
+    xa_replay_env_step then turns into the agent's state, rewards, dones and replay-ring
+    append, as for the other transition envs. Resets draw from Philox keyed by the env's
+    seed and its own device step counter."""
+
+    def __init__(self, env_id='Acrobot-v1', n_envs=1, seed=55, device=None):
+        fused = CLASSIC_ENVS[env_id]
+        n, od = int(n_envs), fused.obs_dim_
+        z = np.zeros((n, 1, od), np.float32)
+        record = (np.zeros((n, od), np.float32), z, z.copy(), np.zeros((n, 1), np.float32),
+                  np.zeros((n, 1), np.float32))
+        self._ready = False
+        super().__init__(env_id, n, (od,), Discrete(3), np.float32, seed=seed, device=device,
+                         record=record)
+        self.kind = fused.kind
+        self.max_episode_steps = fused.max_episode_steps
+        self.spec.max_episode_steps = self.max_episode_steps
+        self.env_seed = int(seed if seed is not None else 0) % 2**64
+        self.state64 = torch.zeros(n, 4, dtype=torch.float64, device=self.device)
+        self.elapsed = torch.zeros(n, dtype=torch.int32, device=self.device)
+        # position of the reset-draw stream: one per env step, read on device (so a
+        # captured rollout draws fresh resets on every replay)
+        self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # pre_step(tensor) validates the actions on the host (one sync per step); raw
+        # pointers (the on-policy rollouts, whose sampler cannot leave [0, 3)) are not
+        self.check_actions = True
+        self._ready = True
+        self.reset()
+
+    def _args(self, reset_only, actions=0, act_ld=1, t=0):
+        from xagents_amd._lib import XaClassicStepArgs
+        a = XaClassicStepArgs()
+        a.env_kind, a.n_envs = self.kind, self.n_envs
+        a.state64, a.elapsed = self.state64.data_ptr(), self.elapsed.data_ptr()
+        a.actions, a.act_ld = actions, act_ld
+        a.seed, a.counter, a.t = self.env_seed, self.step_counter.data_ptr(), t
+        a.max_episode_steps, a.reset_only = self.max_episode_steps, int(reset_only)
+        return a
+
+    def reset(self):
+        """env.reset() of every env into the state. The draw is keyed by the step counter,
+        which only steps advance, so repeated reset() calls without steps in between replay
+        the same initial state (as WalkerVecEnv)."""
+        super().reset()
+        if not self._ready:
+            return self.state
+        import ctypes
+        from xagents_amd._lib import call, stream
+        a = self._args(True, t=-1)  # step index -1: no step's reset draw uses it
+        a.out_post = self.state.data_ptr()
+        call('xa_classic_step', ctypes.byref(a), stream())
+        return self.state
+
+    def pre_step(self, actions=None, act_ld=1):
+        """env.step of every env with `actions` (a device tensor [N] int32, or a pointer to
+        int32 actions at element stride act_ld) into the one-step record."""
+        import ctypes
+        from xagents_amd._lib import call, stream
+        if actions is None:
+            raise ValueError('ClassicControlVecEnv.pre_step needs the step\'s actions')
+        if isinstance(actions, int):
+            ptr = actions
+        else:
+            assert actions.dtype == torch.int32 and actions.is_contiguous() and \
+                actions.numel() == self.n_envs
+            if self.check_actions and not torch.cuda.is_current_stream_capturing():
+                lo, hi = int(actions.min()), int(actions.max())
+                if lo < 0 or hi >= self.action_space.n:
+                    raise ValueError(f'actions must lie in [0, {self.action_space.n}), got '
+                                     f'[{lo}, {hi}]')
+            ptr, act_ld = actions.data_ptr(), 1
+        a = self._args(False, ptr, act_ld)
+        a.out_obs, a.out_post = self.rep_obs.data_ptr(), self.rep_state.data_ptr()
+        a.out_rew, a.out_done = self.rep_rew.data_ptr(), self.rep_done.data_ptr()
+        call('xa_classic_step', ctypes.byref(a), stream())
+        call('xa_counter_bump', self.step_counter.data_ptr(), stream())
+
+
+def create_envs(env_name, n=1, preprocess=False, *args, mode=None, seed=55, device=None,
                 t_rec=4096, **kwargs):
     """Device counterpart of xagents.utils.common.create_envs (common.py:145-166).
 
     Returns ONE vectorized env object of length n (the agents accept it wherever the
-    reference takes a list of gym envs).
+    reference takes a list of gym envs). mode: 'replay' (recorded streams; the default for
+    every id that has them), 'dynamics' (the env stepped on device with the actions; the
+    default for Acrobot-v1 and MountainCar-v0, which have no recorded mode) or
+    'transitions' (the transition-replay surface the layer-executor agents step).
     """
+    if env_name in CLASSIC_ENVS:
+        assert not preprocess, (f'Cannot use AtariWrapper or --preprocess for non-atari '
+                                f'environment {env_name}')
+        if mode is None or mode == 'dynamics':
+            return CLASSIC_ENVS[env_name](n, seed=seed, device=device)
+        if mode == 'transitions':
+            return ClassicControlVecEnv(env_name, n, seed=seed, device=device)
+        raise ValueError(f"{env_name} has no mode {mode!r}: use 'dynamics' (fused rollout) "
+                         f"or 'transitions' (step kernel)")
+    if mode is None:
+        mode = 'replay'
     if 'NoFrameskip' in env_name and preprocess:
         # AtariWrapper on device over a synthetic raw RGB frame stream (atari.py)
         from xagents_amd.atari import AtariFrameVecEnv

@@ -227,7 +227,9 @@ class TRPO(PPO):
             a.done_epret = self.b_epret.data_ptr() + 4 * t
             a.out_ld = T
             if hasattr(env, 'pre_step'):
-                env.pre_step()
+                # raw-frame env / dynamics env (env.step with step t's actions: column t
+                # of the env-major b_act, stride T) into the one-step record
+                env.pre_step(self.b_act.data_ptr() + 4 * t, T)
             call('xa_replay_env_step', ctypes.byref(a), stream())
         call('xa_copy_block', self.b_dstep.data_ptr(), T, self.b_done.data_ptr() + 4, T + 1, N,
              T, stream())
