@@ -46,11 +46,13 @@ import torch
 import torch.distributed as dist
 
 from xagents_amd import kernels
-from xagents_amd._lib import XaAcerArgs, XaReplayStepArgs, call, stream
+from xagents_amd._lib import XaAcerArgs, call, stream
 from xagents_amd.a2c.agent import A2C
 from xagents_amd.base import OnPolicy
 from xagents_amd.envs import Discrete
+from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor
+from xagents_amd.onpolicy_executor import chunked_executors
 
 
 class ACER(A2C):
@@ -103,8 +105,7 @@ class ACER(A2C):
         self.ema_alpha = ema_alpha
         self.batch_dtypes = ['uint8', 'float32', 'int32', 'float32', 'float32']
         self.use_graph = use_graph
-        self._graph = None
-        self._rollout_warm = False
+        self._rollout_phase = CapturedPhase()
         self.executor_path = True
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world_size = dist.get_world_size() if self.distributed else 1
@@ -136,7 +137,6 @@ class ACER(A2C):
         cap = self.buffers[0].size
         self.capacity = cap
         obs_shape = env.obs_shape
-        self.obs_buf = torch.zeros((T + 1, N) + obs_shape, dtype=torch.uint8, device=dev)
         # trajectory ring (one RB1 deque entry per env per train step)
         self.r_frames = torch.zeros((cap, N, T + 1) + obs_shape, dtype=torch.uint8, device=dev)
         self.r_mu = torch.zeros(cap, N, T, A, **f32)
@@ -158,29 +158,16 @@ class ACER(A2C):
         # frame item j = env (T + 1) + t of a trajectory slot <- obs_buf item t N + env
         j = np.arange(N * (T + 1))
         self.frame_perm = torch.from_numpy((j % (T + 1)) * N + j // (T + 1)).to(dev)
-        # rollout bookkeeping (episode statistics)
-        self.b_logp, self.b_ent = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
-        self.b_done = torch.zeros(N, T + 1, **f32)
-        self.b_epret = torch.zeros(N, T, **f32)
-        self.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        seed = self.seed if self.seed is not None else int(np.random.SeedSequence().entropy % 2**63)
-        self.rng_seed = (int(seed) * 1000003 + self.rank * 7919 + 17) % 2**64
+        # frames, sampler outputs and episode bookkeeping of the rollout
+        self._setup_rollout(returns=False)
         self.ex_roll = LayerExecutor(self.model, N)
         self.ex_roll.keep_hidden = False  # forward only
-        self._sa = XaReplayStepArgs()
-        env.fill_step_args(self._sa)
-        self._sa.ring_states = None
         # update: n_envs (T + 1) rows in chunks; chunks keep their activations for backward
         B = N * (T + 1)
         self.B = B
         chunk = min(B, self.CHUNK)
         self.chunk = chunk
-        self.ex_chunks = [LayerExecutor(self.model, min(chunk, B - c0))
-                          for c0 in range(0, B, chunk)]
-        ex0 = self.ex_chunks[0]
-        for ex in self.ex_chunks[1:]:
-            ex.workspace, ex.dcol = ex0.workspace, ex0.dcol
-            ex.douts = [None if d is None else d0[:ex.B] for d, d0 in zip(ex.douts, ex0.douts)]
+        self.ex_chunks = chunked_executors(self.model, B, chunk)
         self.avg_model = self.model.clone()
         self.avg_ex = {}
         if self.trust_region:
@@ -204,33 +191,16 @@ class ACER(A2C):
         """n_steps x [forward, Categorical sample, behaviour logits, env step] into the
         staging buffers; obs_buf[t] = the policy input of step t (step t + 1's input is the
         pre-reset obs of step t), obs_buf[T] = get_states() (the bootstrap frame)."""
-        N, T, A = self.n_envs, self.n_steps, self.n_actions
-        env = self.envs
-        a = self._sa
-        self.obs_buf[0].copy_(env.state)
-        call('xa_copy_block', env.done.data_ptr(), 1, self.b_done.data_ptr(), T + 1, N, 1,
-             stream())
-        act0, mu0 = self.g_act.data_ptr(), self.g_mu.data_ptr()
-        rew0, done0 = self.g_rew.data_ptr(), self.g_done.data_ptr()
-        for t in range(T):
-            outs = self.ex_roll.forward(self.obs_buf[t])
-            logits = outs[self.actor_out]
-            call('xa_categorical', logits.data_ptr(), A, N, A, None,
-                 self.rng_counter.data_ptr(), self.rng_seed, t, None, act0 + 4 * t,
-                 self.b_logp.data_ptr() + 4 * t, self.b_ent.data_ptr() + 4 * t, T, stream())
-            call('xa_copy_block', logits.data_ptr(), A, mu0 + 4 * t * A, T * A, N, A, stream())
-            a.out_new_states = self.obs_buf.data_ptr() + (t + 1) * N * self.ob
-            a.out_rewards = rew0 + 4 * t
-            a.out_dones = done0 + 4 * t
-            a.done_epret = self.b_epret.data_ptr() + 4 * t
-            a.out_ld = T
-            if hasattr(env, 'pre_step'):
-                # raw-frame env / dynamics env (env.step with step t's actions: column t
-                # of the env-major action rows, stride T) into the one-step record
-                env.pre_step(act0 + 4 * t, T)
-            call('xa_replay_env_step', ctypes.byref(a), stream())
-        call('xa_copy_block', done0, T, self.b_done.data_ptr() + 4, T + 1, N, T, stream())
-        self.obs_buf[T].copy_(env.state)
+        T, A = self.n_steps, self.n_actions
+        mu0 = self.g_mu.data_ptr()
+
+        def behaviour_logits(t, outs):
+            call('xa_copy_block', outs[self.actor_out].data_ptr(), A, mu0 + 4 * t * A, T * A,
+                 self.n_envs, A, stream())
+
+        self._rollout_steps(self.ex_roll.forward, behaviour_logits, self.g_act, self.g_rew,
+                            self.g_done, logits_at=self.actor_out)
+        self.obs_buf[T].copy_(self.envs.state)
         kernels.counter_bump(self.rng_counter)
 
     def _play_chunk(self):
@@ -240,23 +210,20 @@ class ACER(A2C):
         self._rollout_kernels()
         return self.g_rew[0].cpu().numpy(), self.g_done[0].cpu().numpy()
 
+    @property
+    def _graph(self):
+        """The captured rollout, or None."""
+        return self._rollout_phase.graph
+
+    def _on_lr_change(self):
+        self._rollout_phase.reset()
+
     def _acer_rollout(self):
         """One rollout (eager the first time, then a captured hipGraph; envs with a host-side
         pre_step stay eager), stored as this step's trajectory ring slot."""
         N, T = self.n_envs, self.n_steps
-        if not self.use_graph or hasattr(self.envs, 'pre_step'):
-            self._rollout_kernels()
-        elif self._graph is not None:
-            self._graph.replay()
-        elif self._rollout_warm:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._rollout_kernels()
-            self._graph = g
-            g.replay()
-        else:
-            self._rollout_kernels()
-            self._rollout_warm = True
+        self._rollout_phase.run(self._rollout_kernels,
+                                self.use_graph and not self.envs.has_pre_step)
         slot = self.count % self.capacity
         call('xa_ring_gather', self.obs_buf.data_ptr(), self.r_frames[slot].data_ptr(),
              self.frame_perm.data_ptr(), N * (T + 1), self.ob, stream())
@@ -332,12 +299,7 @@ class ACER(A2C):
             ex.backward(d, self.grad, batch=ex.B, accumulate=j > 0)
         if self.distributed:
             dist.all_reduce(self.grad)
-        opt = self.model.optimizer
-        call('xa_adam_step_bump', opt.iterations.data_ptr(), stream())
-        kernels.clip_adam(self.model.theta, opt.m, opt.v, self.grad, opt.iterations,
-                          opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon,
-                          clip_norm=self.grad_norm, grad_scale=1.0 / self.world_size,
-                          workspace=self.adam_ws)
+        self._clip_adam()
         # ema.apply: the shadow starts at the variable's value on the first apply
         if self.ema_started:
             call('xa_ema', self.avg_model.theta.data_ptr(), self.model.theta.data_ptr(),

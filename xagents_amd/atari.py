@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from xagents_amd._lib import XaAtariStepArgs, call, stream
-from xagents_amd.envs import Discrete, TransitionReplayVecEnv
+from xagents_amd.envs import Discrete, StepKernelVecEnv
 
 INTER_RESIZE_COEF_BITS = 11
 INTER_RESIZE_COEF_SCALE = 1 << INTER_RESIZE_COEF_BITS
@@ -78,7 +78,7 @@ def record_raw_frames(n_envs, t_raw, height=210, width=160, seed=55, mean_episod
     return frames, rew.astype(np.float32), done
 
 
-class AtariFrameVecEnv(TransitionReplayVecEnv):
+class AtariFrameVecEnv(StepKernelVecEnv):
     """n Atari envs behind AtariWrapper, stepped on device.
 
     Constructor arguments follow AtariWrapper(env, frame_skips=4, resize_shape=(84, 84),
@@ -95,16 +95,10 @@ class AtariFrameVecEnv(TransitionReplayVecEnv):
         self.max_frame = bool(max_frame)
         out_w, out_h = self.frame_shape
         obs_shape = (*self.frame_shape, 1)
-        z = np.zeros((n_envs, 1) + obs_shape, np.uint8)
-        record = (np.zeros((n_envs,) + obs_shape, np.uint8), z, z.copy(),
-                  np.zeros((n_envs, 1), np.float32),
-                  np.zeros((n_envs, 1), np.float32))
         frames, rew, done = raw if raw is not None else record_raw_frames(
             n_envs, t_raw, seed=seed, mean_episode=mean_episode)
         assert frames.shape[0] == n_envs and frames.shape[-1] == 3 and frames.ndim == 5
-        self._raw_ready = False
-        super().__init__(env_id, n_envs, obs_shape, Discrete(n_actions), np.uint8, seed=seed,
-                         device=device, record=record)
+        super().__init__(env_id, n_envs, obs_shape, Discrete(n_actions), np.uint8, device)
         dev = self.device
         self.t_raw, self.raw_h, self.raw_w = frames.shape[1], frames.shape[2], frames.shape[3]
         self.raw_frames = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
@@ -121,15 +115,12 @@ class AtariFrameVecEnv(TransitionReplayVecEnv):
         a.raw_done, a.raw_cursor = self.raw_done.data_ptr(), self.raw_cursor.data_ptr()
         a.skips, a.max_frame = self.skips, int(self.max_frame)
         a.xofs, a.alpha, a.yofs, a.beta = (t.data_ptr() for t in self.tables)
-        self._raw_ready = True
         self.reset()
 
     def reset(self):
         """AtariWrapper.reset for every env: raw cursor to each stream's first (reset)
         frame, processed alone into the state."""
         super().reset()
-        if not self._raw_ready:
-            return self.state
         self.raw_cursor.zero_()
         a = self._args
         a.reset_only = 1
@@ -143,6 +134,5 @@ class AtariFrameVecEnv(TransitionReplayVecEnv):
         does not depend on the actions)."""
         a = self._args
         a.reset_only = 0
-        a.out_step, a.out_post = self.rep_obs.data_ptr(), self.rep_state.data_ptr()
-        a.out_rew, a.out_done = self.rep_rew.data_ptr(), self.rep_done.data_ptr()
+        a.out_step, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
         call('xa_atari_step', ctypes.byref(a), stream())

@@ -732,8 +732,6 @@ class OffPolicy(BaseAgent, ABC):
     def _env_step(self, actions, store=True):
         """One xa_replay_env_step: every env steps with `actions` (device) and, when
         `store`, appends its transition to its replay ring (xagents/base.py:388-426)."""
-        from xagents_amd._lib import call, stream
-        import ctypes
         a = self._step_args
         if store:
             self.replay.fill_step_args(a, actions)
@@ -743,12 +741,7 @@ class OffPolicy(BaseAgent, ABC):
         r = self._st_row
         a.out_dones = self._st_done[r].data_ptr()
         a.done_epret = self._st_epret[r].data_ptr()
-        pre_step = getattr(self.envs, 'pre_step', None)
-        if pre_step is not None:
-            # raw-frame env (AtariWrapper.step) / dynamics env (env.step with the actions)
-            # into the one-step record
-            pre_step(actions)
-        call('xa_replay_env_step', ctypes.byref(a), stream())
+        self.envs.step_into(a, actions)
         if store:
             self.replay.appended()
         self._st_row += 1
@@ -763,8 +756,7 @@ class OffPolicy(BaseAgent, ABC):
         """One xa_replay_env_step with the play policy's actions and no replay append;
         reward / done rows go to play-only buffers, so the training statistics rows and
         the rings are untouched."""
-        from xagents_amd._lib import XaReplayStepArgs, call, stream
-        import ctypes
+        from xagents_amd._lib import XaReplayStepArgs
         if getattr(self, '_play_args', None) is None:
             n = self.n_envs
             self._play_out = torch.zeros(3, n, dtype=torch.float32, device=self.device)
@@ -778,10 +770,7 @@ class OffPolicy(BaseAgent, ABC):
         a = self._play_args
         actions = self._play_actions()
         a.actions, a.act_bytes = actions.data_ptr(), self.replay.act_bytes
-        pre_step = getattr(self.envs, 'pre_step', None)
-        if pre_step is not None:
-            pre_step(actions)
-        call('xa_replay_env_step', ctypes.byref(a), stream())
+        self.envs.step_into(a, actions)
         out = self._play_out[:2, 0].cpu().numpy()
         return out[:1], out[1:]
 

@@ -19,6 +19,7 @@ from xagents_amd import kernels
 from xagents_amd._lib import call, stream
 from xagents_amd.base import OffPolicy
 from xagents_amd.envs import Box
+from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor
 
 
@@ -61,6 +62,7 @@ class DDPG(OffPolicy):
         S = int(np.prod(self.envs.obs_shape))
         A = self.n_actions
         self._setup_offpolicy((A,), np.float32)
+        self._phases = {}  # CapturedPhase of every captured phase, by name
         B = self.n_envs * self.replay.k
         self.batch_size, self.S, self.A = B, S, A
         dev = self.device
@@ -495,25 +497,11 @@ class DDPG(OffPolicy):
     def _run_phase(self, name, fn):
         """Eager once, then captured and replayed. Data-parallel steps stay eager (their
         gradient all-reduce is a torch collective)."""
-        graphs = self.__dict__.setdefault('_graphs', {})
-        warm = self.__dict__.setdefault('_warm', set())
-        if not getattr(self, 'use_graph', True) or self.distributed:
-            fn()
-        elif name in graphs:
-            graphs[name].replay()
-        elif name in warm:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            graphs[name] = g
-            g.replay()
-        else:
-            fn()
-            warm.add(name)
+        self._phases.setdefault(name, CapturedPhase()).run(
+            fn, getattr(self, 'use_graph', True) and not self.distributed)
 
     def _on_lr_change(self):
-        self.__dict__['_graphs'] = {}  # the learning rates are baked into the launches
-        self.__dict__['_warm'] = set()
+        self._phases = {}  # the learning rates are baked into the launches
         self.__dict__.pop('_fused', None)  # (and into the fused step's arguments)
 
     def _setup_step_stage(self):
@@ -568,7 +556,7 @@ class DDPG(OffPolicy):
         episode run gradient_steps (or that env's episode length) gradient steps.
         The env phase is one hipGraph replay (a few small launches at batch n_envs);
         envs with a host-side pre_step (raw-frame Atari) stay on the eager path."""
-        if hasattr(self.envs, 'pre_step'):
+        if self.envs.has_pre_step:
             actions = self.get_step_actions()
             row = self._st_row
             self._env_step(actions)

@@ -24,6 +24,7 @@ from xagents_amd import kernels
 from xagents_amd._lib import call, stream
 from xagents_amd.base import OffPolicy
 from xagents_amd.envs import Discrete
+from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor, adam_apply
 
 
@@ -59,6 +60,7 @@ class DQN(OffPolicy):
 
     def _setup_device(self):
         self._setup_offpolicy((), np.int32)
+        self._learn_captured = CapturedPhase()
         k = self.replay.k
         if self.n_envs * k > 1 and k == 1:
             # ReplayBuffer1.get_sample returns the raw tuple for k == 1 and
@@ -353,19 +355,14 @@ class DQN(OffPolicy):
     def _run_learn(self):
         """Eager once, then captured and replayed as a hipGraph (the sample slots live in a
         fixed device buffer); data-parallel steps stay eager (torch collective)."""
-        if not getattr(self, 'use_graph', True) or self.distributed or not self._learn_graph():
-            self._learn_phase()
-        elif getattr(self, '_lgraph', None) is not None:
-            self._lgraph.replay()
-        elif getattr(self, '_lwarm', False):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._learn_phase()
-            self._lgraph = g
-            g.replay()
-        else:
-            self._learn_phase()
-            self._lwarm = True
+        self._learn_captured.run(
+            self._learn_phase,
+            getattr(self, 'use_graph', True) and not self.distributed and self._learn_graph())
+
+    @property
+    def _lgraph(self):
+        """The captured learner phase, or None."""
+        return self._learn_captured.graph
 
     def _learn_graph(self):
         """Launch the learner phase directly (default: between the eager acting launches a
@@ -377,8 +374,7 @@ class DQN(OffPolicy):
         return self._lg_on
 
     def _on_lr_change(self):
-        self._lgraph = None  # the learning rate is baked into the Adam launch
-        self._lwarm = False
+        self._learn_captured.reset()  # the learning rate is baked into the Adam launch
 
     def at_step_end(self):
         self.sync_target_model()

@@ -18,11 +18,13 @@ all n envs lives in HBM and is stepped inside the fused rollout kernel:
 All expose the gym-like surface the agents use: len(), observation_space.shape,
 action_space (Discrete/Box), seed(), reset().
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from xagents_amd._lib import (XA_ENV_ACROBOT, XA_ENV_CARTPOLE, XA_ENV_MOUNTAINCAR,
-                              XA_ENV_REPLAY)
+                              XA_ENV_REPLAY, XaClassicStepArgs, XaWalkerStepArgs, call, stream)
 from xagents_amd.nets import default_device
 
 
@@ -328,6 +330,14 @@ class TransitionReplayVecEnv:
 
     def __init__(self, env_id, n_envs, obs_shape, action_space, obs_dtype=np.uint8,
                  t_rec=256, seed=55, device=None, record=None, mean_episode=200):
+        self._setup(env_id, n_envs, obs_shape, action_space, obs_dtype, device)
+        record = record or record_transitions(n_envs, t_rec, obs_shape, obs_dtype, seed,
+                                              mean_episode)
+        self._set_record(*(torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+                           for a in record))
+        self.reset()
+
+    def _setup(self, env_id, n_envs, obs_shape, action_space, obs_dtype, device):
         self.spec = EnvSpec(env_id)
         self.n_envs = int(n_envs)
         self.device = torch.device(device) if device is not None else default_device()
@@ -336,19 +346,19 @@ class TransitionReplayVecEnv:
         self.action_space = action_space
         self.obs_dtype = np.dtype(obs_dtype)
         self.obs_shape = tuple(obs_shape)
-        s0, rep_obs, rep_state, rep_rew, rep_done = record or record_transitions(
-            n_envs, t_rec, obs_shape, obs_dtype, seed, mean_episode)
-        self.t_rec = rep_obs.shape[1]
+        self.obs_bytes = int(np.prod(self.obs_shape)) * self.obs_dtype.itemsize
         dev = self.device
-        tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        self.s0, self.rep_obs, self.rep_state = tt(s0), tt(rep_obs), tt(rep_state)
-        self.rep_rew, self.rep_done = tt(rep_rew), tt(rep_done)
-        self.state = torch.empty_like(self.s0)
         self.cursor = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
         self.done = torch.zeros(self.n_envs, dtype=torch.float32, device=dev)
         self.ep_return = torch.zeros(self.n_envs, dtype=torch.float32, device=dev)
-        self.obs_bytes = int(np.prod(self.obs_shape)) * self.obs_dtype.itemsize
-        self.reset()
+
+    def _set_record(self, s0, rep_obs, rep_state, rep_rew, rep_done):
+        """The device record: s0 [N, *obs], rep_obs / rep_state [N, t_rec, *obs], rep_rew /
+        rep_done [N, t_rec] f32."""
+        self.t_rec = rep_obs.shape[1]
+        self.s0, self.rep_obs, self.rep_state = s0, rep_obs, rep_state
+        self.rep_rew, self.rep_done = rep_rew, rep_done
+        self.state = torch.empty_like(s0)
 
     def __len__(self):
         return self.n_envs
@@ -376,8 +386,49 @@ class TransitionReplayVecEnv:
         a.state, a.cursor = self.state.data_ptr(), self.cursor.data_ptr()
         a.ep_return, a.done = self.ep_return.data_ptr(), self.done.data_ptr()
 
+    @property
+    def has_pre_step(self):
+        """Whether a launch of the env's own (pre_step) precedes every xa_replay_env_step."""
+        return getattr(self, 'pre_step', None) is not None
 
-class WalkerVecEnv(TransitionReplayVecEnv):
+    def step_into(self, args, actions=None, act_ld=None):
+        """One env step into `args` (XaReplayStepArgs from fill_step_args, outputs pointed
+        where the caller wants them): the env's pre_step, if it has one, with the step's
+        actions (a device tensor, or a pointer and its stride act_ld), then
+        xa_replay_env_step."""
+        pre_step = getattr(self, 'pre_step', None)  # looked up per call: it may be wrapped
+        if pre_step is not None:
+            # raw-frame env (AtariWrapper.step) / dynamics env (env.step with the actions)
+            # into the one-step record
+            if act_ld is None:
+                pre_step(actions)
+            else:
+                pre_step(actions, act_ld)
+        call('xa_replay_env_step', ctypes.byref(args), stream())
+
+
+class StepKernelVecEnv(TransitionReplayVecEnv):
+    """Base of the envs a kernel of their own steps (pre_step) into a one-step record
+    (t_rec == 1), which xa_replay_env_step then consumes like a recorded transition.
+    Subclasses allocate their state and end their constructor with self.reset()."""
+
+    def __init__(self, env_id, n_envs, obs_shape, action_space, obs_dtype, device=None):
+        self._setup(env_id, n_envs, obs_shape, action_space, obs_dtype, device)
+        n, shape = self.n_envs, self.obs_shape
+        dtype = torch.uint8 if self.obs_dtype == np.uint8 else torch.float32
+        obs = dict(dtype=dtype, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._set_record(torch.zeros((n,) + shape, **obs), torch.zeros((n, 1) + shape, **obs),
+                         torch.zeros((n, 1) + shape, **obs), torch.zeros(n, 1, **f32),
+                         torch.zeros(n, 1, **f32))
+
+    def record_ptrs(self):
+        """(obs, post-reset state, reward, done) of the one-step record."""
+        return (self.rep_obs.data_ptr(), self.rep_state.data_ptr(), self.rep_rew.data_ptr(),
+                self.rep_done.data_ptr())
+
+
+class WalkerVecEnv(StepKernelVecEnv):
     """BipedalWalker-v3 device stand-in (csrc/walker.hip): real
     action-dependent dynamics with BipedalWalker's 24-value observation, 4 motor commands
     in [-1, 1], reward formula and termination (not Box2D: a planar kinematic walker on flat
@@ -386,21 +437,14 @@ class WalkerVecEnv(TransitionReplayVecEnv):
     rewards, dones and replay-ring append, as for the other transition envs."""
 
     def __init__(self, env_id='BipedalWalker-v3', n_envs=1, seed=55, device=None):
-        n = int(n_envs)
-        z = np.zeros((n, 1, 24), np.float32)
-        record = (np.zeros((n, 24), np.float32), z, z.copy(), np.zeros((n, 1), np.float32),
-                  np.zeros((n, 1), np.float32))
-        self._ready = False
-        super().__init__(env_id, n, (24,), Box(-1.0, 1.0, (4,)), np.float32, seed=seed,
-                         device=device, record=record)
+        super().__init__(env_id, n_envs, (24,), Box(-1.0, 1.0, (4,)), np.float32, device)
+        n = self.n_envs
         self.walker_seed = int(seed if seed is not None else 0) % 2**64
         self.walker_state = torch.zeros(n, 18, dtype=torch.float32, device=self.device)
         self.episode = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self._ready = True
         self.reset()
 
     def _args(self, reset_only, actions=0, act_ld=4):
-        from xagents_amd._lib import XaWalkerStepArgs
         a = XaWalkerStepArgs()
         a.n_envs, a.state, a.episode = self.n_envs, self.walker_state.data_ptr(), \
             self.episode.data_ptr()
@@ -413,10 +457,6 @@ class WalkerVecEnv(TransitionReplayVecEnv):
         the env's episode counter, which only a finished episode advances (xa_walker_step),
         so repeated reset() calls without steps in between replay the same initial state."""
         super().reset()
-        if not self._ready:
-            return self.state
-        import ctypes
-        from xagents_amd._lib import call, stream
         a = self._args(True)
         a.out_post = self.state.data_ptr()
         call('xa_walker_step', ctypes.byref(a), stream())
@@ -425,8 +465,6 @@ class WalkerVecEnv(TransitionReplayVecEnv):
     def pre_step(self, actions=None, act_ld=4):
         """env.step of every env with `actions` (a device tensor [N, 4] f32, or a pointer
         to rows of 4 f32 at row stride act_ld) into the one-step record."""
-        import ctypes
-        from xagents_amd._lib import call, stream
         if actions is None:
             raise ValueError('WalkerVecEnv.pre_step needs the step\'s actions')
         ptr = actions if isinstance(actions, int) else actions.data_ptr()
@@ -434,12 +472,11 @@ class WalkerVecEnv(TransitionReplayVecEnv):
             assert actions.dtype == torch.float32 and actions.is_contiguous()
             act_ld = actions.shape[-1]
         a = self._args(False, ptr, act_ld)
-        a.out_obs, a.out_post = self.rep_obs.data_ptr(), self.rep_state.data_ptr()
-        a.out_rew, a.out_done = self.rep_rew.data_ptr(), self.rep_done.data_ptr()
+        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
         call('xa_walker_step', ctypes.byref(a), stream())
 
 
-class ClassicControlVecEnv(TransitionReplayVecEnv):
+class ClassicControlVecEnv(StepKernelVecEnv):
     """Acrobot-v1 / MountainCar-v0 behind the executor env step (csrc/classic_envs.hip): the
     dynamics of AcrobotVecEnv / MountainCarVecEnv, bit for bit, one xa_classic_step launch
     per env step (pre_step, given the step's actions) into the one-step record that
@@ -449,13 +486,8 @@ class ClassicControlVecEnv(TransitionReplayVecEnv):
 
     def __init__(self, env_id='Acrobot-v1', n_envs=1, seed=55, device=None):
         fused = CLASSIC_ENVS[env_id]
-        n, od = int(n_envs), fused.obs_dim_
-        z = np.zeros((n, 1, od), np.float32)
-        record = (np.zeros((n, od), np.float32), z, z.copy(), np.zeros((n, 1), np.float32),
-                  np.zeros((n, 1), np.float32))
-        self._ready = False
-        super().__init__(env_id, n, (od,), Discrete(3), np.float32, seed=seed, device=device,
-                         record=record)
+        super().__init__(env_id, n_envs, (fused.obs_dim_,), Discrete(3), np.float32, device)
+        n = self.n_envs
         self.kind = fused.kind
         self.max_episode_steps = fused.max_episode_steps
         self.spec.max_episode_steps = self.max_episode_steps
@@ -468,11 +500,9 @@ class ClassicControlVecEnv(TransitionReplayVecEnv):
         # pre_step(tensor) validates the actions on the host (one sync per step); raw
         # pointers (the on-policy rollouts, whose sampler cannot leave [0, 3)) are not
         self.check_actions = True
-        self._ready = True
         self.reset()
 
     def _args(self, reset_only, actions=0, act_ld=1, t=0):
-        from xagents_amd._lib import XaClassicStepArgs
         a = XaClassicStepArgs()
         a.env_kind, a.n_envs = self.kind, self.n_envs
         a.state64, a.elapsed = self.state64.data_ptr(), self.elapsed.data_ptr()
@@ -486,10 +516,6 @@ class ClassicControlVecEnv(TransitionReplayVecEnv):
         which only steps advance, so repeated reset() calls without steps in between replay
         the same initial state (as WalkerVecEnv)."""
         super().reset()
-        if not self._ready:
-            return self.state
-        import ctypes
-        from xagents_amd._lib import call, stream
         a = self._args(True, t=-1)  # step index -1: no step's reset draw uses it
         a.out_post = self.state.data_ptr()
         call('xa_classic_step', ctypes.byref(a), stream())
@@ -498,8 +524,6 @@ class ClassicControlVecEnv(TransitionReplayVecEnv):
     def pre_step(self, actions=None, act_ld=1):
         """env.step of every env with `actions` (a device tensor [N] int32, or a pointer to
         int32 actions at element stride act_ld) into the one-step record."""
-        import ctypes
-        from xagents_amd._lib import call, stream
         if actions is None:
             raise ValueError('ClassicControlVecEnv.pre_step needs the step\'s actions')
         if isinstance(actions, int):
@@ -514,8 +538,7 @@ class ClassicControlVecEnv(TransitionReplayVecEnv):
                                      f'[{lo}, {hi}]')
             ptr, act_ld = actions.data_ptr(), 1
         a = self._args(False, ptr, act_ld)
-        a.out_obs, a.out_post = self.rep_obs.data_ptr(), self.rep_state.data_ptr()
-        a.out_rew, a.out_done = self.rep_rew.data_ptr(), self.rep_done.data_ptr()
+        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
         call('xa_classic_step', ctypes.byref(a), stream())
         call('xa_counter_bump', self.step_counter.data_ptr(), stream())
 

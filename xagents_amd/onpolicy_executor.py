@@ -31,7 +31,118 @@ from xagents_amd._lib import (XA_DIST_DIAG_GAUSSIAN, XA_LOSS_PPO, XA_RETURNS_GAE
 from xagents_amd.layers import LayerExecutor
 
 
-class ExecutorActorCritic:
+def chunked_executors(model, rows, chunk):
+    """LayerExecutors for `rows` samples in chunks of <= `chunk` (each chunk keeps its own
+    activations; GEMM index ranges stay 32-bit). The backward buffers are used one chunk at
+    a time, so every chunk shares the first one's."""
+    chunks = [LayerExecutor(model, min(chunk, rows - c0)) for c0 in range(0, rows, chunk)]
+    ex0 = chunks[0]
+    for ex in chunks[1:]:
+        ex.workspace, ex.dcol = ex0.workspace, ex0.dcol
+        ex.douts = [None if d is None else d0[:ex.B] for d, d0 in zip(ex.douts, ex0.douts)]
+    return chunks
+
+
+class ExecutorRollout:
+    """The per-step rollout of every agent whose policy runs on the layer executor (A2C /
+    PPO below, TRPO, ACER): buffers, sampler, env step and bookkeeping in one place; the
+    agents say which model(s) run and where actions, rewards and step dones land."""
+
+    def _setup_rollout(self, returns=True):
+        """Frames, sampler outputs, episode bookkeeping, RNG state and the env-step
+        arguments; returns: also actions, values, rewards and returns (A2C / PPO / TRPO;
+        ACER stages its own)."""
+        env = self.envs
+        N, T, A = self.n_envs, self.n_steps, self.n_actions
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.obs_buf = torch.zeros((T + 1, N) + env.obs_shape, dtype=env.state.dtype,
+                                   device=dev)
+        # Box action spaces: MultivariateNormalDiag(loc = actor output), f32 action rows
+        self.gaussian = getattr(self, 'distribution_type', 'Categorical') != 'Categorical'
+        self.b_logp, self.b_ent = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
+        self.b_done = torch.zeros(N, T + 1, **f32)
+        self.b_epret = torch.zeros(N, T, **f32)
+        if returns:
+            if self.gaussian:
+                self.b_act = torch.zeros(N, T, A, **f32)
+            else:
+                self.b_act = torch.zeros(N, T, dtype=torch.int32, device=dev)
+            self.b_val, self.b_rew = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
+            self.b_dstep = torch.zeros(N, T, **f32)
+            self.b_ret = torch.zeros(N, T, **f32)
+            self.next_val = torch.zeros(N, **f32)
+        self.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        seed = self.seed if self.seed is not None else int(np.random.SeedSequence().entropy % 2**63)
+        self.rng_seed = (int(seed) * 1000003 + self.rank * 7919 + 17) % 2**64
+        self._sa = XaReplayStepArgs()
+        env.fill_step_args(self._sa)
+        self._sa.ring_states = None
+
+    def _rollout_steps(self, forward, extra, act, rew, dstep, logits_at=0, uniforms=None):
+        """n_steps x [forward(obs_buf[t]) -> outputs, sample from outputs[logits_at] into
+        column t of `act`, extra(t, outputs), env step into column t of `rew` / `dstep` and
+        obs_buf[t + 1]]; then dones[:, t + 1] = done of step t (dones[:, 0] is the
+        carried-in flag). act / rew / dstep are env-major [N, T] rows."""
+        N, T, A = self.n_envs, self.n_steps, self.n_actions
+        env, a = self.envs, self._sa
+        self.obs_buf[0].copy_(env.state)
+        call('xa_copy_block', env.done.data_ptr(), 1, self.b_done.data_ptr(), T + 1, N, 1,
+             stream())
+        ob = env.obs_bytes
+        act_w = A if self.gaussian else 1  # 4-byte words per action; rows of T actions
+        act_ld = T * act_w
+        for t in range(T):
+            outs = forward(self.obs_buf[t])
+            logits = outs[logits_at]
+            act_t = act.data_ptr() + 4 * t * act_w
+            if self.gaussian:
+                call('xa_diag_gaussian', logits.data_ptr(), A, N, A, None,
+                     self.rng_counter.data_ptr(), self.rng_seed, t, None, act_ld, act_t,
+                     self.b_logp.data_ptr() + 4 * t, self.b_ent.data_ptr() + 4 * t, T, stream())
+            else:
+                call('xa_categorical', logits.data_ptr(), A, N, A,
+                     None if uniforms is None else uniforms.data_ptr() + 4 * t * N,
+                     self.rng_counter.data_ptr(), self.rng_seed, t, None, act_t,
+                     self.b_logp.data_ptr() + 4 * t, self.b_ent.data_ptr() + 4 * t, T, stream())
+            extra(t, outs)
+            a.out_new_states = self.obs_buf.data_ptr() + (t + 1) * N * ob
+            a.out_rewards = rew.data_ptr() + 4 * t
+            a.out_dones = dstep.data_ptr() + 4 * t
+            a.done_epret = self.b_epret.data_ptr() + 4 * t
+            a.out_ld = T
+            env.step_into(a, act_t, act_ld)
+        call('xa_copy_block', dstep.data_ptr(), T, self.b_done.data_ptr() + 4, T + 1, N, T,
+             stream())
+
+    def _store_value(self, t, value):
+        """value [N, 1] -> values[:, t]."""
+        call('xa_copy_block', value.data_ptr(), 1, self.b_val.data_ptr() + 4 * t,
+             self.n_steps, self.n_envs, 1, stream())
+
+    def _bootstrap_returns(self, value):
+        """next_val = value = V(get_states()), then GAE / n-step returns."""
+        call('xa_copy_block', value.data_ptr(), 1, self.next_val.data_ptr(), 1, self.n_envs, 1,
+             stream())
+        if self.return_kind == XA_RETURNS_GAE:
+            kernels.gae(self.b_rew, self.b_val, self.b_done, self.next_val, self.gamma,
+                        self.lam, out=self.b_ret)
+        else:
+            kernels.nstep_returns(self.b_rew, self.b_done, self.next_val, self.gamma,
+                                  out=self.b_ret)
+        kernels.counter_bump(self.rng_counter)
+
+    def _clip_adam(self):
+        """tf.clip_by_global_norm + Keras Adam on the (all-reduced: 1 / world) gradient."""
+        opt = self.model.optimizer
+        call('xa_adam_step_bump', opt.iterations.data_ptr(), stream())
+        kernels.clip_adam(self.model.theta, opt.m, opt.v, self.grad, opt.iterations,
+                          opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon,
+                          clip_norm=self.grad_norm, grad_scale=1.0 / self.world_size,
+                          workspace=self.adam_ws)
+
+
+class ExecutorActorCritic(ExecutorRollout):
     """Mixin for A2C / PPO when the model is not the fused actor-critic MLP."""
 
     CHUNK = 4096
@@ -46,43 +157,18 @@ class ExecutorActorCritic:
         N, T = self.n_envs, self.n_steps
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        self.obs_buf = torch.zeros((T + 1, N) + env.obs_shape,
-                                   dtype=env.state.dtype, device=dev)
-        # Box action spaces: MultivariateNormalDiag(loc = actor output), f32 action rows
-        self.gaussian = getattr(self, 'distribution_type', 'Categorical') != 'Categorical'
+        self._setup_rollout()
         A = self.n_actions
-        if self.gaussian:
-            self.b_act = torch.zeros(N, T, A, dtype=torch.float32, device=dev)
-        else:
-            self.b_act = torch.zeros(N, T, dtype=torch.int32, device=dev)
-        self.b_logp, self.b_val = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
-        self.b_ent, self.b_rew = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
-        self.b_done = torch.zeros(N, T + 1, **f32)
-        self.b_dstep = torch.zeros(N, T, **f32)
-        self.b_epret = torch.zeros(N, T, **f32)
-        self.b_ret = torch.zeros(N, T, **f32)
-        self.next_val = torch.zeros(N, **f32)
-        self.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        seed = self.seed if self.seed is not None else int(np.random.SeedSequence().entropy % 2**63)
-        self.rng_seed = (int(seed) * 1000003 + self.rank * 7919 + 17) % 2**64
         self.ex_roll = LayerExecutor(self.model, N)
         self.ex_roll.keep_hidden = False  # forward only
-        self._sa = XaReplayStepArgs()
-        env.fill_step_args(self._sa)
-        self._sa.ring_states = None
         B = N * T
         mb = getattr(self, 'mini_batch_size', B)
         self.mb = mb
         self.n_mb = (B + mb - 1) // mb
-        # the update minibatch runs in chunks of <= 4096 samples (each chunk keeps its own
-        # activations; GEMM index ranges stay 32-bit), gradients accumulate over chunks
+        # the update minibatch runs in chunks of <= 4096 samples, gradients accumulate over
+        # chunks
         self.chunk = min(mb, self.CHUNK)
-        self.ex_chunks = [LayerExecutor(self.model, min(self.chunk, mb - c0))
-                          for c0 in range(0, mb, self.chunk)]
-        ex0 = self.ex_chunks[0]
-        for ex in self.ex_chunks[1:]:  # backward buffers are used one chunk at a time
-            ex.workspace, ex.dcol = ex0.workspace, ex0.dcol
-            ex.douts = [None if d is None else d0[:ex.B] for d, d0 in zip(ex.douts, ex0.douts)]
+        self.ex_chunks = chunked_executors(self.model, mb, self.chunk)
         self.mb_logits = torch.zeros(mb, self.n_actions, **f32)
         self.mb_value = torch.zeros(mb, 1, **f32)
         self.mb_obs = torch.zeros((mb,) + env.obs_shape, dtype=env.state.dtype, device=dev)
@@ -111,55 +197,10 @@ class ExecutorActorCritic:
 
     # ---- rollout ------------------------------------------------------------------
     def _executor_rollout(self):
-        N, T = self.n_envs, self.n_steps
-        env = self.envs
-        a = self._sa
-        self.obs_buf[0].copy_(env.state)
-        call('xa_copy_block', env.done.data_ptr(), 1, self.b_done.data_ptr(), T + 1, N, 1,
-             stream())
-        ob = env.obs_bytes
-        for t in range(T):
-            logits, value = self.ex_roll.forward(self.obs_buf[t])
-            A = self.n_actions
-            if self.gaussian:
-                call('xa_diag_gaussian', logits.data_ptr(), A, N, A, None,
-                     self.rng_counter.data_ptr(), self.rng_seed, t, None, T * A,
-                     self.b_act.data_ptr() + 4 * t * A, self.b_logp.data_ptr() + 4 * t,
-                     self.b_ent.data_ptr() + 4 * t, T, stream())
-            else:
-                u = self._exec_uniforms
-                call('xa_categorical', logits.data_ptr(), A, N, A,
-                     None if u is None else u.data_ptr() + 4 * t * N,
-                     self.rng_counter.data_ptr(), self.rng_seed, t, None,
-                     self.b_act.data_ptr() + 4 * t, self.b_logp.data_ptr() + 4 * t,
-                     self.b_ent.data_ptr() + 4 * t, T, stream())
-            call('xa_copy_block', value.data_ptr(), 1, self.b_val.data_ptr() + 4 * t, T, N, 1,
-                 stream())
-            a.out_new_states = self.obs_buf.data_ptr() + (t + 1) * N * ob
-            a.out_rewards = self.b_rew.data_ptr() + 4 * t
-            a.out_dones = self.b_dstep.data_ptr() + 4 * t
-            a.done_epret = self.b_epret.data_ptr() + 4 * t
-            a.out_ld = T  # env-major [N, T] rows
-            if hasattr(env, 'pre_step'):
-                # raw-frame env (AtariWrapper.step) / dynamics env (env.step with step t's
-                # actions: env-major rows of b_act, stride T A) into the one-step record
-                if self.gaussian:
-                    env.pre_step(self.b_act.data_ptr() + 4 * t * A, T * A)
-                else:
-                    env.pre_step(self.b_act.data_ptr() + 4 * t, T)
-            call('xa_replay_env_step', ctypes.byref(a), stream())
-        # dones[:, t + 1] = done of step t (dones[:, 0] is the carried-in flag)
-        call('xa_copy_block', self.b_dstep.data_ptr(), T, self.b_done.data_ptr() + 4, T + 1, N,
-             T, stream())
-        value = self.ex_roll.forward(env.state)[1]
-        call('xa_copy_block', value.data_ptr(), 1, self.next_val.data_ptr(), 1, N, 1, stream())
-        if self.return_kind == XA_RETURNS_GAE:
-            kernels.gae(self.b_rew, self.b_val, self.b_done, self.next_val, self.gamma,
-                        self.lam, out=self.b_ret)
-        else:
-            kernels.nstep_returns(self.b_rew, self.b_done, self.next_val, self.gamma,
-                                  out=self.b_ret)
-        kernels.counter_bump(self.rng_counter)
+        self._rollout_steps(self.ex_roll.forward, lambda t, outs: self._store_value(t, outs[1]),
+                            self.b_act, self.b_rew, self.b_dstep,
+                            uniforms=self._exec_uniforms)
+        self._bootstrap_returns(self.ex_roll.forward(self.envs.state)[1])
 
     # ---- update ---------------------------------------------------------------------
     def _upload_slots(self, flat_idx):
@@ -242,12 +283,7 @@ class ExecutorActorCritic:
                 torch.distributed.all_reduce(self.grad[:self._bucket_hi])
             for w in works:
                 w.wait()
-        opt = self.model.optimizer
-        call('xa_adam_step_bump', opt.iterations.data_ptr(), stream())
-        kernels.clip_adam(self.model.theta, opt.m, opt.v, self.grad, opt.iterations,
-                          opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon,
-                          clip_norm=self.grad_norm, grad_scale=1.0 / self.world_size,
-                          workspace=self.adam_ws)
+        self._clip_adam()
 
     def _bucket_hook(self, works):
         """Backward hook of the last chunk (LayerExecutor.backward on_grad): layers finish

@@ -25,10 +25,10 @@ import numpy as np
 import torch
 
 from xagents_amd import kernels
-from xagents_amd._lib import (XA_RETURNS_GAE, XaReplayStepArgs, XaTrpoHeadArgs, call, load,
-                              stream)
+from xagents_amd._lib import XA_RETURNS_GAE, XaTrpoHeadArgs, call, load, stream
 from xagents_amd.base import OnPolicy
 from xagents_amd.envs import Discrete
+from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor
 from xagents_amd.ppo.agent import PPO
 
@@ -79,7 +79,7 @@ class TRPO(PPO):
         self.value_loss_coef = value_loss_coef
         self.grad_norm = grad_norm
         self.use_graph = use_graph  # rollout replayed from a hipGraph after one eager pass
-        self._rgraph = None
+        self._rollout_phase, self._critic_phase = CapturedPhase(), CapturedPhase()
         self.executor_path = True
         if not isinstance(self.envs[0].action_space, Discrete):
             raise NotImplementedError('Only Categorical(logits) policies are supported')
@@ -108,24 +108,9 @@ class TRPO(PPO):
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         A = self.n_actions
-        self.obs_buf = torch.zeros((T + 1, N) + env.obs_shape, dtype=env.state.dtype,
-                                   device=dev)
-        self.b_act = torch.zeros(N, T, dtype=torch.int32, device=dev)
-        self.b_logp, self.b_val = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
-        self.b_ent, self.b_rew = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
-        self.b_done = torch.zeros(N, T + 1, **f32)
-        self.b_dstep = torch.zeros(N, T, **f32)
-        self.b_epret = torch.zeros(N, T, **f32)
-        self.b_ret = torch.zeros(N, T, **f32)
-        self.next_val = torch.zeros(N, **f32)
-        self.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        seed = self.seed if self.seed is not None else int(np.random.SeedSequence().entropy % 2**63)
-        self.rng_seed = (int(seed) * 1000003 + 17) % 2**64
+        self._setup_rollout()
         self.ex_actor_roll = LayerExecutor(self.actor, N)
         self.ex_critic_roll = LayerExecutor(self.critic, N)
-        self._sa = XaReplayStepArgs()
-        env.fill_step_args(self._sa)
-        self._sa.ring_states = None
         # whole-batch executors (update) and the FVP subsample states[::fvp_n_steps]
         self.ex_actor = LayerExecutor(self.actor, B)
         self.fvp_idx = np.arange(0, B, self.fvp_n_steps)
@@ -182,19 +167,7 @@ class TRPO(PPO):
     def _rollout(self):
         """The rollout launches (~11 per env step) are host-bound when launched one by one
         from Python; after one eager pass they are captured once and replayed."""
-        if not self.use_graph:
-            self._rollout_kernels()
-        elif self._rgraph is not None:
-            self._rgraph.replay()
-        elif getattr(self, '_rollout_warm', False):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._rollout_kernels()
-            self._rgraph = g
-            g.replay()
-        else:
-            self._rollout_kernels()
-            self._rollout_warm = True
+        self._rollout_phase.run(self._rollout_kernels, self.use_graph)
         self.steps += self.n_envs * self.n_steps
         self._queue_episode_stats(self.b_done, self.b_epret)
 
@@ -205,42 +178,17 @@ class TRPO(PPO):
         return self.b_rew[0].cpu().numpy(), self.b_done[0, 1:].cpu().numpy()
 
     def _rollout_kernels(self):
-        N, T = self.n_envs, self.n_steps
-        env, a = self.envs, self._sa
-        self.obs_buf[0].copy_(env.state)
-        call('xa_copy_block', env.done.data_ptr(), 1, self.b_done.data_ptr(), T + 1, N, 1,
-             stream())
-        ob = env.obs_bytes
-        A = self.n_actions
-        for t in range(T):
-            logits = self.ex_actor_roll.forward(self.obs_buf[t])[0]
-            call('xa_categorical', logits.data_ptr(), A, N, A, None, self.rng_counter.data_ptr(),
-                 self.rng_seed, t, None, self.b_act.data_ptr() + 4 * t,
-                 self.b_logp.data_ptr() + 4 * t, self.b_ent.data_ptr() + 4 * t, T, stream())
-            value = self.ex_critic_roll.forward(self.obs_buf[t])[0]
-            call('xa_copy_block', value.data_ptr(), 1, self.b_val.data_ptr() + 4 * t, T, N, 1,
-                 stream())
-            a.actions, a.act_bytes = self.b_act.data_ptr() + 4 * t, 4
-            a.out_new_states = self.obs_buf.data_ptr() + (t + 1) * N * ob
-            a.out_rewards = self.b_rew.data_ptr() + 4 * t
-            a.out_dones = self.b_dstep.data_ptr() + 4 * t
-            a.done_epret = self.b_epret.data_ptr() + 4 * t
-            a.out_ld = T
-            if hasattr(env, 'pre_step'):
-                # raw-frame env / dynamics env (env.step with step t's actions: column t
-                # of the env-major b_act, stride T) into the one-step record
-                env.pre_step(self.b_act.data_ptr() + 4 * t, T)
-            call('xa_replay_env_step', ctypes.byref(a), stream())
-        call('xa_copy_block', self.b_dstep.data_ptr(), T, self.b_done.data_ptr() + 4, T + 1, N,
-             T, stream())
-        value = self.ex_critic_roll.forward(env.state)[0]
-        call('xa_copy_block', value.data_ptr(), 1, self.next_val.data_ptr(), 1, N, 1, stream())
-        kernels.gae(self.b_rew, self.b_val, self.b_done, self.next_val, self.gamma, self.lam,
-                    out=self.b_ret)
-        kernels.counter_bump(self.rng_counter)
+        critic = self.ex_critic_roll.forward
+
+        def value_of(t, outs):
+            self._store_value(t, critic(self.obs_buf[t])[0])
+
+        self._rollout_steps(self.ex_actor_roll.forward, value_of, self.b_act, self.b_rew,
+                            self.b_dstep)
+        self._bootstrap_returns(critic(self.envs.state)[0])
         # env-major batch of the states the reference concatenates (base.py:549-564)
         call('xa_ring_gather', self.obs_buf.data_ptr(), self.batch_states.data_ptr(),
-             self._batch_slots.data_ptr(), self.batch_size, env.obs_bytes, stream())
+             self._batch_slots.data_ptr(), self.batch_size, self.envs.obs_bytes, stream())
 
     # ---- actor pieces ------------------------------------------------------------------
     def _head(self, logits_new, dlogits=None, out=None):
@@ -340,29 +288,16 @@ class TRPO(PPO):
         perms = np.stack([np.random.permutation(B) for _ in range(n_perm)])
         if getattr(self, 'critic_slots', None) is None or self.critic_slots.shape[0] != n_perm:
             self.critic_slots = torch.zeros(n_perm, B, dtype=torch.int64, device=self.device)
-            self._cgraph = None
+            self._critic_phase.reset()  # a capture holds the old slots' address
         self.critic_slots.copy_(torch.from_numpy(perms), non_blocking=False)
-        if not self.use_graph:
-            self._critic_kernels()
-        elif self._cgraph is not None:
-            self._cgraph.replay()
-        elif getattr(self, '_critic_warm', False):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._critic_kernels()
-            self._cgraph = g
-            g.replay()
-        else:
-            self._critic_kernels()
-            self._critic_warm = True
+        self._critic_phase.run(self._critic_kernels, self.use_graph)
 
     def _on_lr_change(self):
         """The plateau reducer changes the LAST output model's learning rate (the critic,
         base.py:277-284); it is a launch argument of the captured critic minibatches, so
         drop the capture (the next update re-warms and re-captures)."""
         super()._on_lr_change()
-        self._cgraph = None
-        self._critic_warm = False
+        self._critic_phase.reset()
 
     def _critic_kernels(self):
         B, mb = self.batch_size, self.mini_batch_size
