@@ -38,6 +38,9 @@ extern "C" {
 #define XA_ENV_CARTPOLE 1 /* CartPole-v1 dynamics on device (gym classic_control semantics) */
 #define XA_ENV_ACROBOT 2  /* Acrobot-v1 dynamics on device (book variant, RK4, obs 6, 3 actions) */
 #define XA_ENV_MOUNTAINCAR 3 /* MountainCar-v0 dynamics on device (obs 2, 3 actions) */
+/* continuous-action ids, stepped by xa_continuous_env_step only (one f32 action per env) */
+#define XA_ENV_PENDULUM 4 /* Pendulum-v1 dynamics on device (obs 3, torque in [-2, 2]) */
+#define XA_ENV_MOUNTAINCAR_CONT 5 /* MountainCarContinuous-v0 on device (obs 2, force in [-1, 1]) */
 
 /* return kinds computed at the end of the fused rollout */
 #define XA_RETURNS_NONE 0
@@ -809,6 +812,48 @@ typedef struct XaClassicStepArgs {
 } XaClassicStepArgs;
 
 int xa_classic_step(const XaClassicStepArgs* args, void* stream);
+
+/* Pendulum-v1 / MountainCarContinuous-v0 on device, one env step per launch, optionally in
+ * the same launch as the replay-ring append: gym's env.step / env.reset of
+ * BaseAgent.step_envs (xagents/base.py:388-426, gym call base.py:408) for the two ids, and
+ * with `step` the rest of step_envs(store_in_buffers=True) as well. The dynamics
+ * (csrc/continuous_envs.hpp) restate gym's classic_control/pendulum.py and
+ * continuous_mountain_car.py in f64; observations and rewards are the f32 rounding.
+ * env_kind = XA_ENV_PENDULUM (obs 3) or XA_ENV_MOUNTAINCAR_CONT (obs 2). state64
+ * [n_envs][2] f64, elapsed [n_envs] int (steps into the episode) and episode [n_envs] int
+ * (finished episodes) are the env's own memory. A step reads env e's raw action at
+ * actions[e * act_ld] (the env clips it as gym does; a non-finite action is the caller's),
+ * applies the TimeLimit max_episode_steps, and a finished env resets from Philox keyed by
+ * (e, its episode counter after the increment; seed): no shared counter, so a captured step
+ * draws fresh resets on every replay. reset_only = 1 resets every env (same key, counter
+ * not advanced) into out_post.
+ *   step == NULL: the returned obs (pre-reset) goes to out_obs [n_envs][obs], reward and
+ *     done to out_rew / out_done, the post-step obs (the reset obs when done) to out_post --
+ *     the one-step record xa_replay_env_step consumes, as xa_classic_step writes it.
+ *   step != NULL: the same launch does what xa_replay_env_step does with that record (ring
+ *     append for both ring kinds, out_states / out_new_states / out_rewards / out_dones /
+ *     done_epret with out_ld, ep_return, done, state <- post), taking the record from
+ *     registers. step->obs_bytes must be 4 * obs and step->n_envs equal n_envs; rep_*, t_rec
+ *     and cursor are ignored and left untouched, as are out_obs / out_post / out_rew /
+ *     out_done here. Not with reset_only. */
+typedef struct XaContinuousStepArgs {
+  int env_kind, n_envs;
+  double* state64;
+  int* elapsed;
+  int* episode;
+  const float* actions;
+  int64_t act_ld; /* floats between envs; the action is element 0 of the row */
+  uint64_t seed;
+  int max_episode_steps;
+  int reset_only;
+  float* out_obs;
+  float* out_post;
+  float* out_rew;
+  float* out_done;
+} XaContinuousStepArgs;
+
+int xa_continuous_env_step(const XaContinuousStepArgs* env, const XaReplayStepArgs* step,
+                           void* stream);
 
 /* Episode statistics to the host (BaseAgent.step_envs bookkeeping, xagents/base.py:388-426):
  * copies n_segments device buffers (bytes a multiple of 4) into pinned host memory in ONE

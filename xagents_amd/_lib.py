@@ -18,6 +18,8 @@ XA_ENV_REPLAY = 0
 XA_ENV_CARTPOLE = 1
 XA_ENV_ACROBOT = 2
 XA_ENV_MOUNTAINCAR = 3
+XA_ENV_PENDULUM = 4
+XA_ENV_MOUNTAINCAR_CONT = 5
 XA_RETURNS_NONE = 0
 XA_RETURNS_GAE = 1
 XA_RETURNS_NSTEP = 2
@@ -271,6 +273,16 @@ class XaClassicStepArgs(Structure):
     ]
 
 
+class XaContinuousStepArgs(Structure):
+    _fields_ = [
+        ('env_kind', c_int), ('n_envs', c_int), ('state64', c_void_p), ('elapsed', c_void_p),
+        ('episode', c_void_p), ('actions', c_void_p), ('act_ld', c_int64), ('seed', c_uint64),
+        ('max_episode_steps', c_int), ('reset_only', c_int),
+        ('out_obs', c_void_p), ('out_post', c_void_p), ('out_rew', c_void_p),
+        ('out_done', c_void_p),
+    ]
+
+
 class XaHostCopyArgs(Structure):
     _fields_ = [
         ('n_segments', c_int), ('src', c_void_p * 4), ('dst', c_void_p * 4),
@@ -504,6 +516,8 @@ _SIGNATURES = {
     'xa_ppo_update_dp_block_bytes': (ctypes.c_size_t, [c_int] * 7),
     'xa_walker_step': (c_int, [POINTER(XaWalkerStepArgs), c_void_p]),
     'xa_classic_step': (c_int, [POINTER(XaClassicStepArgs), c_void_p]),
+    'xa_continuous_env_step': (c_int, [POINTER(XaContinuousStepArgs), POINTER(XaReplayStepArgs),
+                                       c_void_p]),
     'xa_copy_to_host': (c_int, [POINTER(XaHostCopyArgs), c_void_p]),
     'xa_host_device_pointer': (c_int, [c_void_p, POINTER(c_void_p)]),
     'xa_mse_grad': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -543,13 +543,14 @@ class DDPG(OffPolicy):
             self._device_checks()
 
     def _step_phase(self):
-        """get_step_actions + one xa_replay_env_step (ring append) writing the step's
-        done / episode-return row into fixed staging rows (graph-capturable)."""
+        """get_step_actions + the env's one-launch step (xa_replay_env_step, or the dynamics
+        env's own fused step; both append to the ring) writing the step's done /
+        episode-return row into fixed staging rows (graph-capturable)."""
         actions = self.get_step_actions()
         a = self._step_args
         self.replay.fill_step_args(a, actions)
         a.out_dones, a.done_epret = self._stage_ptrs
-        call('xa_replay_env_step', ctypes.byref(a), stream())
+        self.envs.step_into(a, actions)
 
     def train_step(self):
         """ddpg/agent.py:149-166: step every env, then for each env that finished an

@@ -14,6 +14,9 @@ all n envs lives in HBM and is stepped inside the fused rollout kernel:
   and MountainCar-v0 (TimeLimit 200) in the same fused rollout; ClassicControlVecEnv steps
   the same two dynamics one launch per env step (xa_classic_step) for the agents whose
   models run on the layer executor.
+* ContinuousControlVecEnv -- gym Pendulum-v1 (TimeLimit 200) and MountainCarContinuous-v0
+  (TimeLimit 999) for the continuous-action agents; the env step and the replay-ring append
+  are one launch (xa_continuous_env_step).
 
 All expose the gym-like surface the agents use: len(), observation_space.shape,
 action_space (Discrete/Box), seed(), reset().
@@ -24,7 +27,9 @@ import numpy as np
 import torch
 
 from xagents_amd._lib import (XA_ENV_ACROBOT, XA_ENV_CARTPOLE, XA_ENV_MOUNTAINCAR,
-                              XA_ENV_REPLAY, XaClassicStepArgs, XaWalkerStepArgs, call, stream)
+                              XA_ENV_MOUNTAINCAR_CONT, XA_ENV_PENDULUM, XA_ENV_REPLAY,
+                              XaClassicStepArgs, XaContinuousStepArgs, XaWalkerStepArgs, call,
+                              stream)
 from xagents_amd.nets import default_device
 
 
@@ -543,6 +548,94 @@ class ClassicControlVecEnv(StepKernelVecEnv):
         call('xa_counter_bump', self.step_counter.data_ptr(), stream())
 
 
+# id -> (env kind, observation size, action bound, gym's TimeLimit)
+CONTINUOUS_ENVS = {'Pendulum-v1': (XA_ENV_PENDULUM, 3, 2.0, 200),
+                   'MountainCarContinuous-v0': (XA_ENV_MOUNTAINCAR_CONT, 2, 1.0, 999)}
+
+
+class ContinuousControlVecEnv(StepKernelVecEnv):
+    """Pendulum-v1 / MountainCarContinuous-v0 on device (csrc/continuous_envs.hip): f64 state
+    [n, 2], one f32 action per env, clipped by the env as gym does. step_into is ONE
+    xa_continuous_env_step launch doing env.step / env.reset and what xa_replay_env_step does
+    with the result (agent state, rewards, dones, replay-ring append), so the env has no
+    pre_step and the off-policy agents keep it on their staged env phase. fused=False is the
+    two-launch composition the other step-kernel envs use (record_step as pre_step, then
+    xa_replay_env_step), kept for A/B timing and the equality tests: same bits. Resets draw
+    from Philox keyed by the env's seed, its index and its own episode counter.
+    max_episode_steps=None takes the id's TimeLimit."""
+
+    def __init__(self, env_id='Pendulum-v1', n_envs=1, seed=55, device=None,
+                 max_episode_steps=None, fused=True):
+        kind, obs_dim, bound, limit = CONTINUOUS_ENVS[env_id]
+        limit = int(limit if max_episode_steps is None else max_episode_steps)
+        if limit <= 0:
+            raise ValueError(f'max_episode_steps must be > 0, got {max_episode_steps}')
+        super().__init__(env_id, n_envs, (obs_dim,), Box(-bound, bound, (1,)), np.float32, device)
+        n = self.n_envs
+        self.kind = kind
+        self.max_episode_steps = limit
+        self.spec.max_episode_steps = limit
+        self.env_seed = int(seed if seed is not None else 0) % 2**64
+        self.state64 = torch.zeros(n, 2, dtype=torch.float64, device=self.device)
+        self.elapsed = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.fused = bool(fused)
+        if not self.fused:
+            self.pre_step = self.record_step
+        self._step_a = self._args(False)  # the launch arguments of a step, built once
+        self.reset()
+
+    def _args(self, reset_only, actions=0, act_ld=1):
+        a = XaContinuousStepArgs()
+        a.env_kind, a.n_envs = self.kind, self.n_envs
+        a.state64, a.elapsed = self.state64.data_ptr(), self.elapsed.data_ptr()
+        a.episode = self.episode.data_ptr()
+        a.actions, a.act_ld, a.seed = actions, act_ld, self.env_seed
+        a.max_episode_steps, a.reset_only = self.max_episode_steps, int(reset_only)
+        return a
+
+    def reset(self):
+        """env.reset() of every env into the state. The draw is keyed by the env's episode
+        counter, which only a finished episode advances, so repeated reset() calls without
+        steps in between replay the same initial state (as WalkerVecEnv)."""
+        super().reset()
+        a = self._args(True)
+        a.out_post = self.state.data_ptr()
+        call('xa_continuous_env_step', ctypes.byref(a), None, stream())
+        return self.state
+
+    def _step_args_for(self, actions, act_ld):
+        """The step's launch arguments with `actions` (a contiguous f32 device tensor [N, 1]
+        or [N], or a pointer to f32 rows whose element 0 is the action, at row stride act_ld
+        floats)."""
+        if actions is None:
+            raise ValueError('ContinuousControlVecEnv needs the step\'s actions')
+        a = self._step_a
+        if isinstance(actions, int):
+            a.actions, a.act_ld = actions, 1 if act_ld is None else act_ld
+        else:
+            assert actions.dtype == torch.float32 and actions.is_contiguous() and \
+                actions.numel() == self.n_envs
+            a.actions, a.act_ld = actions.data_ptr(), 1
+        return a
+
+    def record_step(self, actions=None, act_ld=1):
+        """env.step of every env with `actions` into the one-step record (the pre_step of
+        the fused=False form)."""
+        a = self._step_args_for(actions, act_ld)
+        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
+        call('xa_continuous_env_step', ctypes.byref(a), None, stream())
+
+    def step_into(self, args, actions=None, act_ld=None):
+        """One env step into `args` (XaReplayStepArgs from fill_step_args, outputs pointed
+        where the caller wants them) in one launch; the two-launch form when the instance
+        has a pre_step (fused=False, or a wrapper someone installed)."""
+        if getattr(self, 'pre_step', None) is not None:
+            return super().step_into(args, actions, act_ld)
+        a = self._step_args_for(actions, act_ld)
+        call('xa_continuous_env_step', ctypes.byref(a), ctypes.byref(args), stream())
+
+
 def create_envs(env_name, n=1, preprocess=False, *args, mode=None, seed=55, device=None,
                 t_rec=4096, **kwargs):
     """Device counterpart of xagents.utils.common.create_envs (common.py:145-166).
@@ -552,6 +645,8 @@ def create_envs(env_name, n=1, preprocess=False, *args, mode=None, seed=55, devi
     every id that has them), 'dynamics' (the env stepped on device with the actions; the
     default for Acrobot-v1 and MountainCar-v0, which have no recorded mode) or
     'transitions' (the transition-replay surface the layer-executor agents step).
+    Pendulum-v1 and MountainCarContinuous-v0 are one env (ContinuousControlVecEnv, which
+    takes max_episode_steps / fused from kwargs) under 'dynamics' and 'transitions' alike.
     """
     if env_name in CLASSIC_ENVS:
         assert not preprocess, (f'Cannot use AtariWrapper or --preprocess for non-atari '
@@ -562,6 +657,13 @@ def create_envs(env_name, n=1, preprocess=False, *args, mode=None, seed=55, devi
             return ClassicControlVecEnv(env_name, n, seed=seed, device=device)
         raise ValueError(f"{env_name} has no mode {mode!r}: use 'dynamics' (fused rollout) "
                          f"or 'transitions' (step kernel)")
+    if env_name in CONTINUOUS_ENVS:
+        assert not preprocess, (f'Cannot use AtariWrapper or --preprocess for non-atari '
+                                f'environment {env_name}')
+        if mode not in (None, 'dynamics', 'transitions'):
+            raise ValueError(f"{env_name} has no mode {mode!r}: use 'dynamics' or "
+                             f"'transitions' (the same step-kernel env)")
+        return ContinuousControlVecEnv(env_name, n, seed=seed, device=device, **kwargs)
     if mode is None:
         mode = 'replay'
     if 'NoFrameskip' in env_name and preprocess:
