@@ -1,15 +1,15 @@
-// gym classic-control dynamics on device: Acrobot-v1 and MountainCar-v0 step, reset and
-// observation functions, shared by the fused rollout (mlp_rollout.hip, one wave per env,
-// wave-uniform) and the step kernel (classic_envs.hip, one thread per env). Replaces gym's
-// env.step / env.reset inside BaseAgent.step_envs (xagents/base.py:388-426, the gym call at
-// base.py:408) for the two ids.
+// gym classic-control dynamics on device: CartPole-v1, Acrobot-v1 and MountainCar-v0 step,
+// reset and observation functions. All three run in the fused rollout (mlp_rollout.hip, one
+// wave per env, wave-uniform); Acrobot and MountainCar also in the step kernel
+// (classic_envs.hip, one thread per env). Replaces gym's env.step / env.reset inside
+// BaseAgent.step_envs (xagents/base.py:388-426, the gym call at base.py:408) for the ids.
 //
-// State and arithmetic are f64, observations the f32 rounding of the f64 values, as for
-// CartPole in mlp_rollout.hip. Every expression is written in one fixed order (the library is
-// compiled with -ffp-contract=off, no fma is wanted here) and the trigonometry is the device
-// library's f64 sin / cos / sincos, so both kernels produce the same bits from the same
-// state and action. The RK4 stages of Acrobot leave [-pi, pi] (|theta| up to ~9 rad), so
-// CartPole's small-angle polynomial does not apply.
+// State and arithmetic are f64, observations the f32 rounding of the f64 values. Every
+// expression is written in one fixed order (the library is compiled with -ffp-contract=off;
+// the only fused multiply-adds are the explicit fma calls of CartPole's small-angle
+// polynomial) and the trigonometry is otherwise the device library's f64 sin / cos / sincos,
+// so both kernels produce the same bits from the same state and action. The RK4 stages of
+// Acrobot leave [-pi, pi] (|theta| up to ~9 rad), so CartPole's polynomial does not apply.
 #pragma once
 #include "../../include/xagents_hip.h"
 #include "xa_common.hpp"
@@ -25,6 +25,58 @@ XA_DEV void xa_reset_uniforms(int env, int t, uint64_t ctr, uint64_t seed, doubl
   const uint32_t rv[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
   for (int k = 0; k < 4; ++k) u[k] = (double)rv[k] * 2.3283064365386963e-10;
+}
+
+// ---- CartPole-v1 (classic_control/cartpole.py): state (x, x_dot, theta, theta_dot), Euler
+// integration. Reward 1 every step, TimeLimit 500.
+// sin and cos of a pole angle: |x| <= 0.5 rad (always, below the 0.2095-rad termination
+// threshold plus one Euler step) by their Taylor series to x^15 / x^16 in Horner form on the
+// f64 FMA unit (truncation < 2.3e-17, within an ulp of libm, like any two libms), larger
+// angles by the library functions. The library sin / cos carry a branch-free Payne-Hanek
+// reduction (~250 f64 instructions) that dominated the per-step dependency chain of the
+// dynamics rollout.
+XA_DEV void pole_sincos(double x, double& sn, double& cs) {
+  if (fabs(x) > 0.5) {
+    sn = sin(x);
+    cs = cos(x);
+    return;
+  }
+  const double x2 = x * x;
+  double ps = 1.0 / 1307674368000.0;               // 1 / 15!
+  ps = fma(ps, -x2, 1.0 / 6227020800.0);           // 1 / 13!
+  ps = fma(ps, -x2, 1.0 / 39916800.0);             // 1 / 11!
+  ps = fma(ps, -x2, 1.0 / 362880.0);               // 1 / 9!
+  ps = fma(ps, -x2, 1.0 / 5040.0);                 // 1 / 7!
+  ps = fma(ps, -x2, 1.0 / 120.0);                  // 1 / 5!
+  ps = fma(ps, -x2, 1.0 / 6.0);                    // 1 / 3!
+  sn = fma(-x * x2, ps, x);
+  double pc = 1.0 / 20922789888000.0;              // 1 / 16!
+  pc = fma(pc, -x2, 1.0 / 87178291200.0);          // 1 / 14!
+  pc = fma(pc, -x2, 1.0 / 479001600.0);            // 1 / 12!
+  pc = fma(pc, -x2, 1.0 / 3628800.0);              // 1 / 10!
+  pc = fma(pc, -x2, 1.0 / 40320.0);                // 1 / 8!
+  pc = fma(pc, -x2, 1.0 / 720.0);                  // 1 / 6!
+  pc = fma(pc, -x2, 1.0 / 24.0);                   // 1 / 4!
+  pc = fma(pc, -x2, 0.5);                          // 1 / 2!
+  cs = fma(-x2, pc, 1.0);
+}
+
+XA_DEV bool cartpole_step(double (&s)[4], int action) {
+  const double gravity = 9.8, masspole = 0.1, total_mass = 1.1, length = 0.5;
+  const double polemass_length = 0.05, force_mag = 10.0, tau = 0.02;
+  const double force = action == 1 ? force_mag : -force_mag;
+  double sintheta, costheta;
+  pole_sincos(s[2], sintheta, costheta);
+  const double temp = (force + polemass_length * s[3] * s[3] * sintheta) / total_mass;
+  const double thetaacc = (gravity * sintheta - costheta * temp) /
+                          (length * (4.0 / 3.0 - masspole * costheta * costheta / total_mass));
+  const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
+  s[0] = s[0] + tau * s[1];
+  s[1] = s[1] + tau * xacc;
+  s[2] = s[2] + tau * s[3];
+  s[3] = s[3] + tau * thetaacc;
+  const double theta_thr = 12.0 * 2.0 * 3.141592653589793 / 360.0;
+  return s[0] < -2.4 || s[0] > 2.4 || s[2] < -theta_thr || s[2] > theta_thr;
 }
 
 // ---- MountainCar-v0 (classic_control/mountain_car.py): state (position, velocity) in
@@ -124,11 +176,28 @@ XA_DEV void xa_acrobot_obs(const double (&s)[4], float (&o)[6]) {
   o[5] = (float)s[3];
 }
 
-// One interface over the two ids (KIND = XA_ENV_ACROBOT / XA_ENV_MOUNTAINCAR): observation
-// and action counts, env.step (returns gym's `terminated`; the caller adds the TimeLimit),
-// the step's reward, env.reset from four uniforms, the observation.
+// One interface over the ids (KIND = XA_ENV_CARTPOLE / XA_ENV_ACROBOT / XA_ENV_MOUNTAINCAR;
+// xa_classic_step takes the last two): observation and action counts, env.step (returns
+// gym's `terminated`; the caller adds the TimeLimit), the step's reward, env.reset from four
+// uniforms, the observation.
 template <int KIND>
 struct XaClassicEnv;
+
+template <>
+struct XaClassicEnv<XA_ENV_CARTPOLE> {
+  static constexpr int kObs = 4, kActions = 2;
+  static XA_DEV bool step(double (&s)[4], int action) { return cartpole_step(s, action); }
+  static XA_DEV float reward(bool) { return 1.0f; }
+  // np_random.uniform(-0.05, 0.05, size=(4,))
+  static XA_DEV void reset(double (&s)[4], const double (&u)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = -0.05 + 0.1 * u[k];
+  }
+  static XA_DEV void obs(const double (&s)[4], float (&o)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (float)s[k];
+  }
+};
 
 template <>
 struct XaClassicEnv<XA_ENV_ACROBOT> {

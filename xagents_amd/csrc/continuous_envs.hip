@@ -3,16 +3,32 @@
 // executor). Replaces gym's env.step / env.reset inside BaseAgent.step_envs
 // (xagents/base.py:388-426, the gym call at base.py:408) for the two ids -- and, given the
 // replay step's arguments, the rest of step_envs(store_in_buffers=True) in the same launch:
-// what replay_step_small_kernel (offpolicy.hip) does with the one-step record, taken from
-// registers instead, so a dynamics env costs one launch per step and not two.
+// the bookkeeping of env_step.hpp that replay_step_small_kernel (offpolicy.hip) does with the
+// one-step record, fed from registers instead, so a dynamics env costs one launch per step
+// and not two.
 //
 // Thread e owns every word of env e (its f64 state, counters, agent state row, ring slot,
 // output rows): no workgroup reads a word another one writes, and the reset draw is keyed by
 // the env's own episode counter, so there is no shared counter to bump between launches.
 #include "../../include/xagents_hip.h"
 #include "continuous_envs.hpp"
+#include "env_step.hpp"
 
 namespace {
+
+// an env's whole observation, one element of xa_step_move. Copied float by float: the
+// 12-byte aggregate copy is otherwise a memcpy through a stack slot, which lands in LDS
+template <int N>
+struct ObsRow {
+  float v[N];
+  ObsRow() = default;
+  XA_DEV ObsRow(const ObsRow& o) { *this = o; }
+  XA_DEV ObsRow& operator=(const ObsRow& o) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = o.v[k];
+    return *this;
+  }
+};
 
 template <int KIND, bool FUSED>
 __global__ __launch_bounds__(256) void continuous_step_kernel(XaContinuousStepArgs a,
@@ -23,21 +39,21 @@ __global__ __launch_bounds__(256) void continuous_step_kernel(XaContinuousStepAr
   if (e >= a.n_envs) return;
   double s[2] = {a.state64[(size_t)e * 2], a.state64[(size_t)e * 2 + 1]};
   int el = a.elapsed[e];
-  float o[OBS], post[OBS];
+  ObsRow<OBS> o, post;
   if (!FUSED && a.reset_only) {
     double u[4];
     xa_reset_uniforms(e, a.episode[e], 0ull, a.seed, u);
     Env::reset(s, u);
     el = 0;
-    Env::obs(s, post);
+    Env::obs(s, post.v);
 #pragma unroll
-    for (int k = 0; k < OBS; ++k) a.out_post[(size_t)e * OBS + k] = post[k];
+    for (int k = 0; k < OBS; ++k) a.out_post[(size_t)e * OBS + k] = post.v[k];
   } else {
     double reward;
     const bool terminated = Env::step(s, (double)a.actions[(size_t)e * a.act_ld], reward);
     el = el + 1;
     const bool done = terminated || el >= a.max_episode_steps;  // gym TimeLimit
-    Env::obs(s, o);  // the obs env.step returns (pre-reset)
+    Env::obs(s, o.v);  // the obs env.step returns (pre-reset)
     if (done) {
       const int ep = a.episode[e] + 1;
       a.episode[e] = ep;
@@ -46,60 +62,21 @@ __global__ __launch_bounds__(256) void continuous_step_kernel(XaContinuousStepAr
       Env::reset(s, u);
       el = 0;
     }
-    Env::obs(s, post);
+    Env::obs(s, post.v);
     const float rew = (float)reward, d = done ? 1.0f : 0.0f;
     if (!FUSED) {
 #pragma unroll
       for (int k = 0; k < OBS; ++k) {
-        a.out_obs[(size_t)e * OBS + k] = o[k];
-        a.out_post[(size_t)e * OBS + k] = post[k];
+        a.out_obs[(size_t)e * OBS + k] = o.v[k];
+        a.out_post[(size_t)e * OBS + k] = post.v[k];
       }
       a.out_rew[e] = rew;
       a.out_done[e] = d;
     } else {
-      // BaseAgent.step_envs' bookkeeping, as replay_step_small_kernel: the old state is read
-      // before the post-step observation replaces it
-      float* st = (float*)r.state + (size_t)e * OBS;
-      float old[OBS];
-#pragma unroll
-      for (int k = 0; k < OBS; ++k) old[k] = st[k];
-      if (r.ring_states) {
-        const int64_t cnt = r.ring_count[e];
-        const int64_t slot = (int64_t)e * r.capacity + cnt % r.capacity;
-        float* rs = (float*)r.ring_states + slot * OBS;
-        float* rn = (float*)r.ring_new_states + slot * OBS;
-#pragma unroll
-        for (int k = 0; k < OBS; ++k) {
-          rs[k] = old[k];
-          rn[k] = o[k];
-        }
-        const uint8_t* src = (const uint8_t*)r.actions + (int64_t)e * r.act_bytes;
-        uint8_t* dst = (uint8_t*)r.ring_actions + slot * r.act_bytes;
-        for (int64_t b = 0; b < r.act_bytes; ++b) dst[b] = src[b];
-        r.ring_rewards[slot] = rew;
-        r.ring_dones[slot] = d;
-        r.ring_count[e] = r.ring_kind == XA_RING_RB2 ? (cnt < r.capacity ? cnt + 1 : cnt) : cnt + 1;
-      }
-      if (r.out_states) {
-        float* os = (float*)r.out_states + (size_t)e * OBS;
-#pragma unroll
-        for (int k = 0; k < OBS; ++k) os[k] = old[k];
-      }
-      if (r.out_new_states) {
-        float* on = (float*)r.out_new_states + (size_t)e * OBS;
-#pragma unroll
-        for (int k = 0; k < OBS; ++k) on[k] = o[k];
-      }
-#pragma unroll
-      for (int k = 0; k < OBS; ++k) st[k] = post[k];
-      const int64_t row = (int64_t)e * (r.out_ld > 0 ? r.out_ld : 1);
-      if (r.out_rewards) r.out_rewards[row] = rew;
-      if (r.out_dones) r.out_dones[row] = d;
-      float ep_ret = r.ep_return[e] + rew;
-      if (r.done_epret) r.done_epret[row] = d != 0.0f ? ep_ret : 0.0f;
-      if (d != 0.0f) ep_ret = 0.0f;
-      r.ep_return[e] = ep_ret;
-      r.done[e] = d;
+      // BaseAgent.step_envs' bookkeeping (env_step.hpp), the env's observation as one element
+      const int64_t slot = xa_step_ring_slot(r, e);
+      xa_step_move<ObsRow<OBS>>(r, e, slot, 0, o, post);
+      xa_step_scalars(r, e, slot, rew, d);
     }
   }
   a.state64[(size_t)e * 2] = s[0];

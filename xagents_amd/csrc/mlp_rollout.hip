@@ -15,7 +15,7 @@
 //   h2_j = tanh(sum of 8 interleaved 8-long fma chains + b2_j)
 //   h2 -> the wave's LDS row of this step (a [64 steps][64 units] chunk buffer)
 //   logit_a = butterfly_sum_j(h2_j * W3[j][a]) + b3_a (the sample needs them)
-//   inverse-CDF sample, then the env's f64 dynamics (RollEnv<kind>)
+//   inverse-CDF sample, then the env's f64 dynamics (XaClassicEnv<kind>, classic_envs.hpp)
 // and once per 64-step chunk, lane j on step t0 + j: the value head from the step's h2
 // row, summed in the pairwise order of the wave butterfly (bitwise the same sums as
 // in-step); softmax, log-prob and entropy. Envs are independent, so no inter-wave
@@ -259,79 +259,6 @@ XA_DEV CatOut<A> categorical(const float (&l)[A], float u, int given_action) {
   return CatOut<A>{act, logp, ent};
 }
 
-// sin and cos of a pole angle: |x| <= 0.5 rad (always, below the 0.2095-rad termination
-// threshold plus one Euler step) by their Taylor series to x^15 / x^16 in Horner form on the
-// f64 FMA unit (truncation < 2.3e-17, within an ulp of libm, like any two libms), larger
-// angles by the library functions. The library sin / cos carry a branch-free Payne-Hanek
-// reduction (~250 f64 instructions) that dominated the per-step dependency chain of the
-// dynamics rollout.
-XA_DEV void pole_sincos(double x, double& sn, double& cs) {
-  if (fabs(x) > 0.5) {
-    sn = sin(x);
-    cs = cos(x);
-    return;
-  }
-  const double x2 = x * x;
-  double ps = 1.0 / 1307674368000.0;               // 1 / 15!
-  ps = fma(ps, -x2, 1.0 / 6227020800.0);           // 1 / 13!
-  ps = fma(ps, -x2, 1.0 / 39916800.0);             // 1 / 11!
-  ps = fma(ps, -x2, 1.0 / 362880.0);               // 1 / 9!
-  ps = fma(ps, -x2, 1.0 / 5040.0);                 // 1 / 7!
-  ps = fma(ps, -x2, 1.0 / 120.0);                  // 1 / 5!
-  ps = fma(ps, -x2, 1.0 / 6.0);                    // 1 / 3!
-  sn = fma(-x * x2, ps, x);
-  double pc = 1.0 / 20922789888000.0;              // 1 / 16!
-  pc = fma(pc, -x2, 1.0 / 87178291200.0);          // 1 / 14!
-  pc = fma(pc, -x2, 1.0 / 479001600.0);            // 1 / 12!
-  pc = fma(pc, -x2, 1.0 / 3628800.0);              // 1 / 10!
-  pc = fma(pc, -x2, 1.0 / 40320.0);                // 1 / 8!
-  pc = fma(pc, -x2, 1.0 / 720.0);                  // 1 / 6!
-  pc = fma(pc, -x2, 1.0 / 24.0);                   // 1 / 4!
-  pc = fma(pc, -x2, 0.5);                          // 1 / 2!
-  cs = fma(-x2, pc, 1.0);
-}
-
-// gym CartPole-v1 (classic_control/cartpole.py), Euler integration in f64.
-XA_DEV bool cartpole_step(double (&s)[4], int action) {
-  const double gravity = 9.8, masspole = 0.1, total_mass = 1.1, length = 0.5;
-  const double polemass_length = 0.05, force_mag = 10.0, tau = 0.02;
-  const double force = action == 1 ? force_mag : -force_mag;
-  double sintheta, costheta;
-  pole_sincos(s[2], sintheta, costheta);
-  const double temp = (force + polemass_length * s[3] * s[3] * sintheta) / total_mass;
-  const double thetaacc = (gravity * sintheta - costheta * temp) /
-                          (length * (4.0 / 3.0 - masspole * costheta * costheta / total_mass));
-  const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
-  s[0] = s[0] + tau * s[1];
-  s[1] = s[1] + tau * xacc;
-  s[2] = s[2] + tau * s[3];
-  s[3] = s[3] + tau * thetaacc;
-  const double theta_thr = 12.0 * 2.0 * 3.141592653589793 / 360.0;
-  return s[0] < -2.4 || s[0] > 2.4 || s[2] < -theta_thr || s[2] > theta_thr;
-}
-
-// The dynamics envs of the step loop: step (gym's `terminated`; the loop adds the TimeLimit),
-// the step's reward, reset from the step's four reset uniforms, observation. Acrobot-v1 and
-// MountainCar-v0 are classic_envs.hpp's, shared with xa_classic_step.
-template <int KIND>
-struct RollEnv : XaClassicEnv<KIND> {};
-
-template <>
-struct RollEnv<XA_ENV_CARTPOLE> {
-  static constexpr int kObs = 4, kActions = 2;
-  static XA_DEV bool step(double (&s)[4], int action) { return cartpole_step(s, action); }
-  static XA_DEV float reward(bool) { return 1.0f; }
-  // np_random.uniform(-0.05, 0.05, size=(4,))
-  static XA_DEV void reset(double (&s)[4], const double (&u)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = -0.05 + 0.1 * u[k];
-  }
-  static XA_DEV void obs(const double (&s)[4], float (&o)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (float)s[k];
-  }
-};
-
 // The sampling uniforms of 64 consecutive steps, lane j holding step t0 + j, fetched a
 // chunk ahead and read back per step with readlane (no memory access on the step chain).
 struct StepChunk {
@@ -358,7 +285,7 @@ XA_DEV float xa_readlane(float v, int l) {
 // the dynamics envs (the next input depends on the sampled action)
 template <int OBS, int A, int KIND>
 __global__ __launch_bounds__(64 * kRollWaves) void mlp_rollout_kernel(XaRolloutArgs p) {
-  using Env = RollEnv<KIND>;
+  using Env = XaClassicEnv<KIND>;
   static_assert(Env::kObs == OBS && Env::kActions == A, "env kind and network shape disagree");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int AH = A + 1, AHP = (AH + 3) & ~3;

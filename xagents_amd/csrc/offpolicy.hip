@@ -9,6 +9,7 @@
 //     reproduces the reference's index semantics lives on the host; the kernels move
 //     the bytes.
 #include "../../include/xagents_hip.h"
+#include "env_step.hpp"
 #include "xa_common.hpp"
 
 namespace {
@@ -190,16 +191,25 @@ __global__ __launch_bounds__(256) void act_grad_kernel(const float* __restrict__
 }
 
 // ---- off-policy replay env step + ring store (BaseAgent.step_envs with
-// store_in_buffers, xagents/base.py:388-426) -----------------------------------------
-XA_DEV int64_t ring_slot(const XaReplayStepArgs& a, int i) {
-  const int64_t cnt = a.ring_count[i];
-  // RB1 deque: the append lands after the newest element; RB2: row current_size % size,
-  // current_size saturating at size -> row 0 once full (buffers.py:133-135)
-  return a.ring_kind == XA_RING_RB2 ? (cnt % a.capacity) : (cnt % a.capacity);
+// store_in_buffers, xagents/base.py:388-426): the bookkeeping is env_step.hpp's ---------
+
+// elements [lo, hi) (Ts) of env i's observation, spread over the workgroup: the record at
+// cursor c supplies the stepped and the post-reset observation
+template <typename T>
+XA_DEV void replay_move(const XaReplayStepArgs& a, int i, int c, int64_t slot, int64_t lo,
+                        int64_t hi) {
+  const int64_t rec = (int64_t)i * a.t_rec + c;
+  const T* s_new = xa_step_row<const T>(a.rep_obs, rec, a.obs_bytes);
+  const T* s_post = xa_step_row<const T>(a.rep_state, rec, a.obs_bytes);
+  for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x)
+    xa_step_move<T>(a, i, slot, e, s_new[e], s_post[e]);
 }
 
-XA_DEV void copy_bytes(uint8_t* d, const uint8_t* s, int64_t n, int64_t lo, int64_t hi) {
-  for (int64_t e = lo + threadIdx.x; e < hi && e < n; e += blockDim.x) d[e] = s[e];
+// the record's reward and done into env i's scalars, then the cursor moves on
+XA_DEV void replay_scalars(const XaReplayStepArgs& a, int i, int c, int64_t slot) {
+  const int64_t rec = (int64_t)i * a.t_rec + c;
+  xa_step_scalars(a, i, slot, a.rep_rew[rec], a.rep_done[rec]);
+  a.cursor[i] = c + 1 < a.t_rec ? c + 1 : 0;
 }
 
 // phase 1: frames (grid: byte chunks x envs); every block reads and writes only its own
@@ -207,138 +217,42 @@ XA_DEV void copy_bytes(uint8_t* d, const uint8_t* s, int64_t n, int64_t lo, int6
 __global__ __launch_bounds__(256) void replay_step_frames_kernel(XaReplayStepArgs a,
                                                                  int64_t chunk) {
   const int i = blockIdx.y;
-  const int64_t lo = blockIdx.x * chunk, hi = lo + chunk;
   const int64_t ob = a.obs_bytes;
+  const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < ob ? lo + chunk : ob;
   const int c = a.cursor[i];
-  const uint8_t* s_new = (const uint8_t*)a.rep_obs + ((int64_t)i * a.t_rec + c) * ob;
-  const uint8_t* s_post = (const uint8_t*)a.rep_state + ((int64_t)i * a.t_rec + c) * ob;
-  uint8_t* st = (uint8_t*)a.state + (int64_t)i * ob;
-  // stage this chunk of the old state (register per byte slot: <= 16 per thread)
-  const bool vec = (ob & 15) == 0 && (chunk & 15) == 0;
-  if (vec) {
-    const int64_t lo16 = lo >> 4, hi16 = (hi < ob ? hi : ob) >> 4;
-    for (int64_t e = lo16 + threadIdx.x; e < hi16; e += blockDim.x) {
-      const uint4 old = reinterpret_cast<const uint4*>(st)[e];
-      const uint4 nw = reinterpret_cast<const uint4*>(s_new)[e];
-      const uint4 post = reinterpret_cast<const uint4*>(s_post)[e];
-      if (a.ring_states) {
-        const int64_t slot = (int64_t)i * a.capacity + ring_slot(a, i);
-        reinterpret_cast<uint4*>((uint8_t*)a.ring_states + slot * ob)[e] = old;
-        reinterpret_cast<uint4*>((uint8_t*)a.ring_new_states + slot * ob)[e] = nw;
-      }
-      if (a.out_states) reinterpret_cast<uint4*>((uint8_t*)a.out_states + (int64_t)i * ob)[e] = old;
-      if (a.out_new_states)
-        reinterpret_cast<uint4*>((uint8_t*)a.out_new_states + (int64_t)i * ob)[e] = nw;
-      reinterpret_cast<uint4*>(st)[e] = post;
-    }
-  } else {
-    for (int64_t e = lo + threadIdx.x; e < hi && e < ob; e += blockDim.x) {
-      const uint8_t old = st[e], nw = s_new[e], post = s_post[e];
-      if (a.ring_states) {
-        const int64_t slot = (int64_t)i * a.capacity + ring_slot(a, i);
-        ((uint8_t*)a.ring_states)[slot * ob + e] = old;
-        ((uint8_t*)a.ring_new_states)[slot * ob + e] = nw;
-      }
-      if (a.out_states) ((uint8_t*)a.out_states)[(int64_t)i * ob + e] = old;
-      if (a.out_new_states) ((uint8_t*)a.out_new_states)[(int64_t)i * ob + e] = nw;
-      st[e] = post;
-    }
-  }
+  const int64_t slot = xa_step_ring_slot(a, i);
+  if ((ob & 15) == 0 && (chunk & 15) == 0)
+    replay_move<uint4>(a, i, c, slot, lo >> 4, hi >> 4);
+  else
+    replay_move<uint8_t>(a, i, c, slot, lo, hi);
 }
 
 // phase 2: per-env scalars, ring scalars, cursor / counters (one thread per env)
 __global__ void replay_step_scalars_kernel(XaReplayStepArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_envs) return;
-  const int c = a.cursor[i];
-  const float r = a.rep_rew[(int64_t)i * a.t_rec + c];
-  const float d = a.rep_done[(int64_t)i * a.t_rec + c];
-  if (a.ring_states) {
-    const int64_t slot = (int64_t)i * a.capacity + ring_slot(a, i);
-    const uint8_t* src = (const uint8_t*)a.actions + (int64_t)i * a.act_bytes;
-    uint8_t* dst = (uint8_t*)a.ring_actions + slot * a.act_bytes;
-    for (int64_t e = 0; e < a.act_bytes; ++e) dst[e] = src[e];
-    a.ring_rewards[slot] = r;
-    a.ring_dones[slot] = d;
-    const int64_t cnt = a.ring_count[i];
-    a.ring_count[i] = a.ring_kind == XA_RING_RB2 ? (cnt < a.capacity ? cnt + 1 : cnt) : cnt + 1;
-  }
-  const int64_t o = (int64_t)i * (a.out_ld > 0 ? a.out_ld : 1);
-  if (a.out_rewards) a.out_rewards[o] = r;
-  if (a.out_dones) a.out_dones[o] = d;
-  float ep = a.ep_return[i] + r;
-  if (a.done_epret) a.done_epret[o] = d != 0.0f ? ep : 0.0f;
-  if (d != 0.0f) ep = 0.0f;
-  a.ep_return[i] = ep;
-  a.done[i] = d;
-  a.cursor[i] = c + 1 < a.t_rec ? c + 1 : 0;
+  replay_scalars(a, i, a.cursor[i], xa_step_ring_slot(a, i));
 }
 
 // small observations (vector envs): both phases in ONE launch, one workgroup per env -- the
-// frame bytes of env i by its workgroup, then its scalars by thread 0 (the cursor is read
-// by every thread before thread 0 advances it behind the barrier)
+// frame bytes of env i by its workgroup, then its scalars by thread 0 (the cursor and the
+// ring slot are read by every thread before thread 0 advances them behind the barrier)
 __global__ __launch_bounds__(256) void replay_step_small_kernel(XaReplayStepArgs a) {
   const int i = blockIdx.x;
   const int64_t ob = a.obs_bytes;
   const int c = a.cursor[i];
-  const uint8_t* s_new = (const uint8_t*)a.rep_obs + ((int64_t)i * a.t_rec + c) * ob;
-  const uint8_t* s_post = (const uint8_t*)a.rep_state + ((int64_t)i * a.t_rec + c) * ob;
-  uint8_t* st = (uint8_t*)a.state + (int64_t)i * ob;
-  const int64_t slot = a.ring_states ? (int64_t)i * a.capacity + ring_slot(a, i) : 0;
+  const int64_t slot = xa_step_ring_slot(a, i);
   const uintptr_t bases = (uintptr_t)a.state | (uintptr_t)a.rep_obs | (uintptr_t)a.rep_state |
                           (uintptr_t)a.ring_states | (uintptr_t)a.ring_new_states |
                           (uintptr_t)a.out_states | (uintptr_t)a.out_new_states;
-  if ((ob & 15) == 0 && (bases & 15) == 0) {
-    // 16-B moves (frames: 7056 B = 441 per env): every address is a 16-B aligned base plus
-    // a multiple of ob
-    const int64_t n16 = ob >> 4;
-    for (int64_t e = threadIdx.x; e < n16; e += blockDim.x) {
-      const uint4 old = reinterpret_cast<const uint4*>(st)[e];
-      const uint4 nw = reinterpret_cast<const uint4*>(s_new)[e];
-      const uint4 post = reinterpret_cast<const uint4*>(s_post)[e];
-      if (a.ring_states) {
-        reinterpret_cast<uint4*>((uint8_t*)a.ring_states + slot * ob)[e] = old;
-        reinterpret_cast<uint4*>((uint8_t*)a.ring_new_states + slot * ob)[e] = nw;
-      }
-      if (a.out_states) reinterpret_cast<uint4*>((uint8_t*)a.out_states + (int64_t)i * ob)[e] = old;
-      if (a.out_new_states)
-        reinterpret_cast<uint4*>((uint8_t*)a.out_new_states + (int64_t)i * ob)[e] = nw;
-      reinterpret_cast<uint4*>(st)[e] = post;
-    }
-  } else {
-    for (int64_t e = threadIdx.x; e < ob; e += blockDim.x) {
-      const uint8_t old = st[e], nw = s_new[e], post = s_post[e];
-      if (a.ring_states) {
-        ((uint8_t*)a.ring_states)[slot * ob + e] = old;
-        ((uint8_t*)a.ring_new_states)[slot * ob + e] = nw;
-      }
-      if (a.out_states) ((uint8_t*)a.out_states)[(int64_t)i * ob + e] = old;
-      if (a.out_new_states) ((uint8_t*)a.out_new_states)[(int64_t)i * ob + e] = nw;
-      st[e] = post;
-    }
-  }
-  __syncthreads();  // (ring_slot and the cursor above were read before the scalars advance them)
-  if (threadIdx.x != 0) return;
-  const float r = a.rep_rew[(int64_t)i * a.t_rec + c];
-  const float d = a.rep_done[(int64_t)i * a.t_rec + c];
-  if (a.ring_states) {
-    const uint8_t* src = (const uint8_t*)a.actions + (int64_t)i * a.act_bytes;
-    uint8_t* dst = (uint8_t*)a.ring_actions + slot * a.act_bytes;
-    for (int64_t e = 0; e < a.act_bytes; ++e) dst[e] = src[e];
-    a.ring_rewards[slot] = r;
-    a.ring_dones[slot] = d;
-    const int64_t cnt = a.ring_count[i];
-    a.ring_count[i] = a.ring_kind == XA_RING_RB2 ? (cnt < a.capacity ? cnt + 1 : cnt) : cnt + 1;
-  }
-  const int64_t o = (int64_t)i * (a.out_ld > 0 ? a.out_ld : 1);
-  if (a.out_rewards) a.out_rewards[o] = r;
-  if (a.out_dones) a.out_dones[o] = d;
-  float ep = a.ep_return[i] + r;
-  if (a.done_epret) a.done_epret[o] = d != 0.0f ? ep : 0.0f;
-  if (d != 0.0f) ep = 0.0f;
-  a.ep_return[i] = ep;
-  a.done[i] = d;
-  a.cursor[i] = c + 1 < a.t_rec ? c + 1 : 0;
+  // 16-B moves (frames: 7056 B = 441 per env) where every address is a 16-B aligned base
+  // plus a multiple of ob
+  if ((ob & 15) == 0 && (bases & 15) == 0)
+    replay_move<uint4>(a, i, c, slot, 0, ob >> 4);
+  else
+    replay_move<uint8_t>(a, i, c, slot, 0, ob);
+  __syncthreads();
+  if (threadIdx.x == 0) replay_scalars(a, i, c, slot);
 }
 
 // dst[r][c] = src[r][c] for a rows x cols block (concat / column slices of [B, n] rows)

@@ -137,25 +137,21 @@ def record_cartpole_replay(n_envs, t_rec, seed=55, max_episode_steps=500):
     return s0, rep_obs, rep_state, rep_rew, rep_done
 
 
-class DeviceVecEnv:
-    """Common device-side env state: the reference's BaseAgent.states / dones /
-    episode_rewards arrays (xagents/base.py:105-113) kept in HBM."""
+class VecEnvBase:
+    """The gym-like surface the agents use (len(), envs[0].observation_space, seed(), spec)
+    and the reference's per-env BaseAgent.dones / episode_rewards (xagents/base.py:105-113)
+    with the record cursor, kept in HBM."""
 
-    kind = None
-
-    def __init__(self, env_id, n_envs, obs_shape, action_space, device=None):
+    def __init__(self, env_id, n_envs, observation_space, action_space, device=None):
         self.spec = EnvSpec(env_id)
         self.n_envs = int(n_envs)
         self.device = torch.device(device) if device is not None else default_device()
-        self.observation_space = Box(-np.inf, np.inf, obs_shape)
+        self.observation_space = observation_space
         self.action_space = action_space
-        self.obs_dim = int(np.prod(obs_shape))
         n, dev = self.n_envs, self.device
-        self.state = torch.zeros(n, self.obs_dim, dtype=torch.float32, device=dev)
         self.done = torch.zeros(n, dtype=torch.float32, device=dev)
         self.cursor = torch.zeros(n, dtype=torch.int32, device=dev)
         self.ep_return = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.state64 = None
         self._seed = None
 
     def __len__(self):
@@ -170,6 +166,25 @@ class DeviceVecEnv:
     def seed(self, seed):
         self._seed = seed
         self.action_space.seed(seed)
+
+    def _zero_episode_state(self):
+        self.cursor.zero_()
+        self.done.zero_()
+        self.ep_return.zero_()
+
+
+class DeviceVecEnv(VecEnvBase):
+    """The envs of the fused rollout: the reference's BaseAgent.states (xagents/base.py:105-113)
+    as an f32 row per env."""
+
+    kind = None
+
+    def __init__(self, env_id, n_envs, obs_shape, action_space, device=None):
+        super().__init__(env_id, n_envs, Box(-np.inf, np.inf, obs_shape), action_space, device)
+        self.obs_dim = int(np.prod(obs_shape))
+        self.state = torch.zeros(self.n_envs, self.obs_dim, dtype=torch.float32,
+                                 device=self.device)
+        self.state64 = None
 
     def fill_rollout_args(self, a):
         a.env_kind = self.kind
@@ -198,9 +213,7 @@ class ReplayVecEnv(DeviceVecEnv):
 
     def reset(self):
         self.state.copy_(self.s0)
-        self.cursor.zero_()
-        self.done.zero_()
-        self.ep_return.zero_()
+        self._zero_episode_state()
         return self.state
 
     def fill_rollout_args(self, a):
@@ -212,38 +225,14 @@ class ReplayVecEnv(DeviceVecEnv):
         a.t_rec = self.t_rec
 
 
-class CartPoleVecEnv(DeviceVecEnv):
-    kind = XA_ENV_CARTPOLE
-    max_episode_steps = 500
-
-    def __init__(self, n_envs=1, seed=None, device=None):
-        super().__init__('CartPole-v1', n_envs, (4,), Discrete(2), device)
-        self.state64 = torch.zeros(self.n_envs, 4, dtype=torch.float64, device=self.device)
-        self._seed = seed
-        self.reset()
-
-    def reset(self):
-        rng = np.random.default_rng(self._seed)
-        s = rng.uniform(-0.05, 0.05, (self.n_envs, 4))
-        self.state64.copy_(torch.from_numpy(s))
-        self.state.copy_(torch.from_numpy(s.astype(np.float32)))
-        self.cursor.zero_()
-        self.done.zero_()
-        self.ep_return.zero_()
-        return self.state
-
-    def fill_rollout_args(self, a):
-        super().fill_rollout_args(a)
-        a.env_state64 = self.state64.data_ptr()
-        a.max_episode_steps = self.max_episode_steps
-
-
 def classic_initial_state(kind, n_envs, rng):
-    """env.reset() of n_envs Acrobot-v1 / MountainCar-v0 envs from a numpy generator: the
-    f64 state [n, 4] (MountainCar: position, velocity = 0, two unused slots) and its f32
-    observation."""
+    """env.reset() of n_envs CartPole-v1 / Acrobot-v1 / MountainCar-v0 envs from a numpy
+    generator: the f64 state [n, 4] (MountainCar: position, velocity = 0, two unused slots)
+    and its f32 observation."""
     s = np.zeros((n_envs, 4))
-    if kind == XA_ENV_ACROBOT:
+    if kind == XA_ENV_CARTPOLE:
+        s[:] = obs = rng.uniform(-0.05, 0.05, (n_envs, 4))
+    elif kind == XA_ENV_ACROBOT:
         s[:] = rng.uniform(-0.1, 0.1, (n_envs, 4))
         obs = np.stack([np.cos(s[:, 0]), np.sin(s[:, 0]), np.cos(s[:, 1]), np.sin(s[:, 1]),
                         s[:, 2], s[:, 3]], 1)
@@ -254,15 +243,16 @@ def classic_initial_state(kind, n_envs, rng):
 
 
 class ClassicDynamicsVecEnv(DeviceVecEnv):
-    """Acrobot-v1 / MountainCar-v0 dynamics in the fused rollout (csrc/classic_envs.hpp):
-    f64 state [n, 4] on device, the policy sees its f32 observation; 3 actions."""
+    """CartPole-v1 / Acrobot-v1 / MountainCar-v0 dynamics in the fused rollout
+    (csrc/classic_envs.hpp): f64 state [n, 4] on device, the policy sees its f32 observation."""
 
     env_id = None
     obs_dim_ = None
+    n_actions = 3
     max_episode_steps = None
 
     def __init__(self, n_envs=1, seed=None, device=None):
-        super().__init__(self.env_id, n_envs, (self.obs_dim_,), Discrete(3), device)
+        super().__init__(self.env_id, n_envs, (self.obs_dim_,), Discrete(self.n_actions), device)
         self.spec.max_episode_steps = self.max_episode_steps
         self.state64 = torch.zeros(self.n_envs, 4, dtype=torch.float64, device=self.device)
         self._seed = seed
@@ -272,15 +262,18 @@ class ClassicDynamicsVecEnv(DeviceVecEnv):
         s, obs = classic_initial_state(self.kind, self.n_envs, np.random.default_rng(self._seed))
         self.state64.copy_(torch.from_numpy(s))
         self.state.copy_(torch.from_numpy(obs))
-        self.cursor.zero_()
-        self.done.zero_()
-        self.ep_return.zero_()
+        self._zero_episode_state()
         return self.state
 
     def fill_rollout_args(self, a):
         super().fill_rollout_args(a)
         a.env_state64 = self.state64.data_ptr()
         a.max_episode_steps = self.max_episode_steps
+
+
+class CartPoleVecEnv(ClassicDynamicsVecEnv):
+    kind = XA_ENV_CARTPOLE
+    env_id, obs_dim_, n_actions, max_episode_steps = 'CartPole-v1', 4, 2, 500
 
 
 class AcrobotVecEnv(ClassicDynamicsVecEnv):
@@ -327,7 +320,7 @@ def record_transitions(n_envs, t_rec, obs_shape, dtype, seed=55, mean_episode=20
     return s0, rep_obs, rep_state, rep_rew.astype(np.float32), rep_done
 
 
-class TransitionReplayVecEnv:
+class TransitionReplayVecEnv(VecEnvBase):
     """Off-policy device env over pre-recorded transitions (Atari-shaped uint8 frames
     or continuous-control f32 vectors). Stepping -- and the replay-ring append of
     BaseAgent.step_envs(store_in_buffers=True), xagents/base.py:388-426 -- is one
@@ -343,19 +336,12 @@ class TransitionReplayVecEnv:
         self.reset()
 
     def _setup(self, env_id, n_envs, obs_shape, action_space, obs_dtype, device):
-        self.spec = EnvSpec(env_id)
-        self.n_envs = int(n_envs)
-        self.device = torch.device(device) if device is not None else default_device()
         low, high = (0, 255) if np.dtype(obs_dtype) == np.uint8 else (-np.inf, np.inf)
-        self.observation_space = Box(low, high, obs_shape, obs_dtype)
-        self.action_space = action_space
+        VecEnvBase.__init__(self, env_id, n_envs, Box(low, high, obs_shape, obs_dtype),
+                            action_space, device)
         self.obs_dtype = np.dtype(obs_dtype)
         self.obs_shape = tuple(obs_shape)
         self.obs_bytes = int(np.prod(self.obs_shape)) * self.obs_dtype.itemsize
-        dev = self.device
-        self.cursor = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
-        self.done = torch.zeros(self.n_envs, dtype=torch.float32, device=dev)
-        self.ep_return = torch.zeros(self.n_envs, dtype=torch.float32, device=dev)
 
     def _set_record(self, s0, rep_obs, rep_state, rep_rew, rep_done):
         """The device record: s0 [N, *obs], rep_obs / rep_state [N, t_rec, *obs], rep_rew /
@@ -365,23 +351,9 @@ class TransitionReplayVecEnv:
         self.rep_rew, self.rep_done = rep_rew, rep_done
         self.state = torch.empty_like(s0)
 
-    def __len__(self):
-        return self.n_envs
-
-    def __getitem__(self, i):
-        return self
-
-    def __iter__(self):
-        return iter([self] * self.n_envs)
-
-    def seed(self, seed):
-        self.action_space.seed(seed)
-
     def reset(self):
         self.state.copy_(self.s0)
-        self.cursor.zero_()
-        self.done.zero_()
-        self.ep_return.zero_()
+        self._zero_episode_state()
         return self.state
 
     def fill_step_args(self, a):
@@ -433,55 +405,83 @@ class StepKernelVecEnv(TransitionReplayVecEnv):
                 self.rep_done.data_ptr())
 
 
-class WalkerVecEnv(StepKernelVecEnv):
+class DynamicsStepVecEnv(StepKernelVecEnv):
+    """Base of the envs whose dynamics a step kernel of their own evaluates with the step's
+    actions: the entry point, its argument struct and the action layout (act_width elements of
+    act_dtype per env) are class attributes, _fill_args points the struct at the env's own
+    memory. Resets draw from Philox keyed by the env's seed and a device counter that only
+    steps or finished episodes advance."""
+
+    entry = args_type = act_dtype = act_width = None
+
+    def __init__(self, env_id, n_envs, obs_shape, action_space, seed, device):
+        super().__init__(env_id, n_envs, obs_shape, action_space, np.float32, device)
+        self.env_seed = int(seed if seed is not None else 0) % 2**64
+
+    def _args(self, reset_only, actions=0, act_ld=None):
+        a = self.args_type()
+        a.n_envs, a.seed, a.reset_only = self.n_envs, self.env_seed, int(reset_only)
+        a.actions, a.act_ld = actions, self.act_width if act_ld is None else act_ld
+        self._fill_args(a)
+        return a
+
+    def _launch(self, a):
+        call(self.entry, ctypes.byref(a), stream())
+
+    def reset(self):
+        """env.reset() of every env into the state. The draw's counter does not move without
+        steps, so repeated reset() calls without steps in between replay the same initial
+        state."""
+        super().reset()
+        a = self._args(True)
+        a.out_post = self.state.data_ptr()
+        self._launch(a)
+        return self.state
+
+    def _action_ptr(self, actions, act_ld=None):
+        """(pointer, stride in elements between envs) of the step's actions: a contiguous
+        device tensor of n_envs x act_width act_dtype elements, or a raw pointer and its
+        act_ld."""
+        if actions is None:
+            raise ValueError(f'{type(self).__name__} needs the step\'s actions')
+        if isinstance(actions, int):
+            return actions, self.act_width if act_ld is None else act_ld
+        assert actions.dtype == self.act_dtype and actions.is_contiguous() and \
+            actions.numel() == self.n_envs * self.act_width
+        return actions.data_ptr(), self.act_width
+
+    def record_step(self, actions=None, act_ld=None):
+        """env.step of every env with `actions` into the one-step record (the pre_step of the
+        two-launch step)."""
+        a = self._args(False, *self._action_ptr(actions, act_ld))
+        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
+        self._launch(a)
+
+
+class WalkerVecEnv(DynamicsStepVecEnv):
     """BipedalWalker-v3 device stand-in (csrc/walker.hip): real
     action-dependent dynamics with BipedalWalker's 24-value observation, 4 motor commands
     in [-1, 1], reward formula and termination (not Box2D: a planar kinematic walker on flat
     ground). Each env step is one xa_walker_step launch (pre_step, given the step's actions)
     into the one-step record that xa_replay_env_step then turns into the agent's state,
-    rewards, dones and replay-ring append, as for the other transition envs."""
+    rewards, dones and replay-ring append, as for the other transition envs. The initial push
+    is drawn from the env's episode counter, which only a finished episode advances."""
+
+    entry, args_type, act_dtype, act_width = 'xa_walker_step', XaWalkerStepArgs, torch.float32, 4
+    pre_step = DynamicsStepVecEnv.record_step
 
     def __init__(self, env_id='BipedalWalker-v3', n_envs=1, seed=55, device=None):
-        super().__init__(env_id, n_envs, (24,), Box(-1.0, 1.0, (4,)), np.float32, device)
-        n = self.n_envs
-        self.walker_seed = int(seed if seed is not None else 0) % 2**64
-        self.walker_state = torch.zeros(n, 18, dtype=torch.float32, device=self.device)
-        self.episode = torch.zeros(n, dtype=torch.int32, device=self.device)
+        super().__init__(env_id, n_envs, (24,), Box(-1.0, 1.0, (4,)), seed, device)
+        self.walker_seed = self.env_seed
+        self.walker_state = torch.zeros(self.n_envs, 18, dtype=torch.float32, device=self.device)
+        self.episode = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
         self.reset()
 
-    def _args(self, reset_only, actions=0, act_ld=4):
-        a = XaWalkerStepArgs()
-        a.n_envs, a.state, a.episode = self.n_envs, self.walker_state.data_ptr(), \
-            self.episode.data_ptr()
-        a.actions, a.act_ld, a.seed, a.reset_only = actions, act_ld, self.walker_seed, \
-            int(reset_only)
-        return a
-
-    def reset(self):
-        """BipedalWalker.reset of every env into the state. The initial push is drawn from
-        the env's episode counter, which only a finished episode advances (xa_walker_step),
-        so repeated reset() calls without steps in between replay the same initial state."""
-        super().reset()
-        a = self._args(True)
-        a.out_post = self.state.data_ptr()
-        call('xa_walker_step', ctypes.byref(a), stream())
-        return self.state
-
-    def pre_step(self, actions=None, act_ld=4):
-        """env.step of every env with `actions` (a device tensor [N, 4] f32, or a pointer
-        to rows of 4 f32 at row stride act_ld) into the one-step record."""
-        if actions is None:
-            raise ValueError('WalkerVecEnv.pre_step needs the step\'s actions')
-        ptr = actions if isinstance(actions, int) else actions.data_ptr()
-        if not isinstance(actions, int):
-            assert actions.dtype == torch.float32 and actions.is_contiguous()
-            act_ld = actions.shape[-1]
-        a = self._args(False, ptr, act_ld)
-        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
-        call('xa_walker_step', ctypes.byref(a), stream())
+    def _fill_args(self, a):
+        a.state, a.episode = self.walker_state.data_ptr(), self.episode.data_ptr()
 
 
-class ClassicControlVecEnv(StepKernelVecEnv):
+class ClassicControlVecEnv(DynamicsStepVecEnv):
     """Acrobot-v1 / MountainCar-v0 behind the executor env step (csrc/classic_envs.hip): the
     dynamics of AcrobotVecEnv / MountainCarVecEnv, bit for bit, one xa_classic_step launch
     per env step (pre_step, given the step's actions) into the one-step record that
@@ -489,16 +489,16 @@ class ClassicControlVecEnv(StepKernelVecEnv):
     append, as for the other transition envs. Resets draw from Philox keyed by the env's
     seed and its own device step counter."""
 
+    entry, args_type, act_dtype, act_width = 'xa_classic_step', XaClassicStepArgs, torch.int32, 1
+
     def __init__(self, env_id='Acrobot-v1', n_envs=1, seed=55, device=None):
         fused = CLASSIC_ENVS[env_id]
-        super().__init__(env_id, n_envs, (fused.obs_dim_,), Discrete(3), np.float32, device)
-        n = self.n_envs
+        super().__init__(env_id, n_envs, (fused.obs_dim_,), Discrete(3), seed, device)
         self.kind = fused.kind
         self.max_episode_steps = fused.max_episode_steps
         self.spec.max_episode_steps = self.max_episode_steps
-        self.env_seed = int(seed if seed is not None else 0) % 2**64
-        self.state64 = torch.zeros(n, 4, dtype=torch.float64, device=self.device)
-        self.elapsed = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.state64 = torch.zeros(self.n_envs, 4, dtype=torch.float64, device=self.device)
+        self.elapsed = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
         # position of the reset-draw stream: one per env step, read on device (so a
         # captured rollout draws fresh resets on every replay)
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -507,44 +507,22 @@ class ClassicControlVecEnv(StepKernelVecEnv):
         self.check_actions = True
         self.reset()
 
-    def _args(self, reset_only, actions=0, act_ld=1, t=0):
-        a = XaClassicStepArgs()
-        a.env_kind, a.n_envs = self.kind, self.n_envs
+    def _fill_args(self, a):
+        a.env_kind, a.max_episode_steps = self.kind, self.max_episode_steps
         a.state64, a.elapsed = self.state64.data_ptr(), self.elapsed.data_ptr()
-        a.actions, a.act_ld = actions, act_ld
-        a.seed, a.counter, a.t = self.env_seed, self.step_counter.data_ptr(), t
-        a.max_episode_steps, a.reset_only = self.max_episode_steps, int(reset_only)
-        return a
+        # step index of the launch's reset draws; -1 for reset(): no step's draw uses it
+        a.counter, a.t = self.step_counter.data_ptr(), -1 if a.reset_only else 0
 
-    def reset(self):
-        """env.reset() of every env into the state. The draw is keyed by the step counter,
-        which only steps advance, so repeated reset() calls without steps in between replay
-        the same initial state (as WalkerVecEnv)."""
-        super().reset()
-        a = self._args(True, t=-1)  # step index -1: no step's reset draw uses it
-        a.out_post = self.state.data_ptr()
-        call('xa_classic_step', ctypes.byref(a), stream())
-        return self.state
-
-    def pre_step(self, actions=None, act_ld=1):
+    def pre_step(self, actions=None, act_ld=None):
         """env.step of every env with `actions` (a device tensor [N] int32, or a pointer to
         int32 actions at element stride act_ld) into the one-step record."""
-        if actions is None:
-            raise ValueError('ClassicControlVecEnv.pre_step needs the step\'s actions')
-        if isinstance(actions, int):
-            ptr = actions
-        else:
-            assert actions.dtype == torch.int32 and actions.is_contiguous() and \
-                actions.numel() == self.n_envs
-            if self.check_actions and not torch.cuda.is_current_stream_capturing():
-                lo, hi = int(actions.min()), int(actions.max())
-                if lo < 0 or hi >= self.action_space.n:
-                    raise ValueError(f'actions must lie in [0, {self.action_space.n}), got '
-                                     f'[{lo}, {hi}]')
-            ptr, act_ld = actions.data_ptr(), 1
-        a = self._args(False, ptr, act_ld)
-        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
-        call('xa_classic_step', ctypes.byref(a), stream())
+        if not isinstance(actions, int) and actions is not None and self.check_actions and \
+                not torch.cuda.is_current_stream_capturing():
+            lo, hi = int(actions.min()), int(actions.max())
+            if lo < 0 or hi >= self.action_space.n:
+                raise ValueError(f'actions must lie in [0, {self.action_space.n}), got '
+                                 f'[{lo}, {hi}]')
+        self.record_step(actions, act_ld)
         call('xa_counter_bump', self.step_counter.data_ptr(), stream())
 
 
@@ -553,7 +531,7 @@ CONTINUOUS_ENVS = {'Pendulum-v1': (XA_ENV_PENDULUM, 3, 2.0, 200),
                    'MountainCarContinuous-v0': (XA_ENV_MOUNTAINCAR_CONT, 2, 1.0, 999)}
 
 
-class ContinuousControlVecEnv(StepKernelVecEnv):
+class ContinuousControlVecEnv(DynamicsStepVecEnv):
     """Pendulum-v1 / MountainCarContinuous-v0 on device (csrc/continuous_envs.hip): f64 state
     [n, 2], one f32 action per env, clipped by the env as gym does. step_into is ONE
     xa_continuous_env_step launch doing env.step / env.reset and what xa_replay_env_step does
@@ -564,67 +542,40 @@ class ContinuousControlVecEnv(StepKernelVecEnv):
     from Philox keyed by the env's seed, its index and its own episode counter.
     max_episode_steps=None takes the id's TimeLimit."""
 
+    entry, args_type = 'xa_continuous_env_step', XaContinuousStepArgs
+    act_dtype, act_width = torch.float32, 1
+
     def __init__(self, env_id='Pendulum-v1', n_envs=1, seed=55, device=None,
                  max_episode_steps=None, fused=True):
         kind, obs_dim, bound, limit = CONTINUOUS_ENVS[env_id]
         limit = int(limit if max_episode_steps is None else max_episode_steps)
         if limit <= 0:
             raise ValueError(f'max_episode_steps must be > 0, got {max_episode_steps}')
-        super().__init__(env_id, n_envs, (obs_dim,), Box(-bound, bound, (1,)), np.float32, device)
-        n = self.n_envs
+        super().__init__(env_id, n_envs, (obs_dim,), Box(-bound, bound, (1,)), seed, device)
         self.kind = kind
         self.max_episode_steps = limit
         self.spec.max_episode_steps = limit
-        self.env_seed = int(seed if seed is not None else 0) % 2**64
-        self.state64 = torch.zeros(n, 2, dtype=torch.float64, device=self.device)
-        self.elapsed = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.episode = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.state64 = torch.zeros(self.n_envs, 2, dtype=torch.float64, device=self.device)
+        self.elapsed = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
         self.fused = bool(fused)
         if not self.fused:
             self.pre_step = self.record_step
         self._step_a = self._args(False)  # the launch arguments of a step, built once
         self.reset()
 
-    def _args(self, reset_only, actions=0, act_ld=1):
-        a = XaContinuousStepArgs()
-        a.env_kind, a.n_envs = self.kind, self.n_envs
+    def _fill_args(self, a):
+        a.env_kind, a.max_episode_steps = self.kind, self.max_episode_steps
         a.state64, a.elapsed = self.state64.data_ptr(), self.elapsed.data_ptr()
         a.episode = self.episode.data_ptr()
-        a.actions, a.act_ld, a.seed = actions, act_ld, self.env_seed
-        a.max_episode_steps, a.reset_only = self.max_episode_steps, int(reset_only)
-        return a
 
-    def reset(self):
-        """env.reset() of every env into the state. The draw is keyed by the env's episode
-        counter, which only a finished episode advances, so repeated reset() calls without
-        steps in between replay the same initial state (as WalkerVecEnv)."""
-        super().reset()
-        a = self._args(True)
-        a.out_post = self.state.data_ptr()
-        call('xa_continuous_env_step', ctypes.byref(a), None, stream())
-        return self.state
+    def _launch(self, a, step=None):
+        call(self.entry, ctypes.byref(a), None if step is None else ctypes.byref(step), stream())
 
     def _step_args_for(self, actions, act_ld):
-        """The step's launch arguments with `actions` (a contiguous f32 device tensor [N, 1]
-        or [N], or a pointer to f32 rows whose element 0 is the action, at row stride act_ld
-        floats)."""
-        if actions is None:
-            raise ValueError('ContinuousControlVecEnv needs the step\'s actions')
         a = self._step_a
-        if isinstance(actions, int):
-            a.actions, a.act_ld = actions, 1 if act_ld is None else act_ld
-        else:
-            assert actions.dtype == torch.float32 and actions.is_contiguous() and \
-                actions.numel() == self.n_envs
-            a.actions, a.act_ld = actions.data_ptr(), 1
+        a.actions, a.act_ld = self._action_ptr(actions, act_ld)
         return a
-
-    def record_step(self, actions=None, act_ld=1):
-        """env.step of every env with `actions` into the one-step record (the pre_step of
-        the fused=False form)."""
-        a = self._step_args_for(actions, act_ld)
-        a.out_obs, a.out_post, a.out_rew, a.out_done = self.record_ptrs()
-        call('xa_continuous_env_step', ctypes.byref(a), None, stream())
 
     def step_into(self, args, actions=None, act_ld=None):
         """One env step into `args` (XaReplayStepArgs from fill_step_args, outputs pointed
@@ -632,8 +583,7 @@ class ContinuousControlVecEnv(StepKernelVecEnv):
         has a pre_step (fused=False, or a wrapper someone installed)."""
         if getattr(self, 'pre_step', None) is not None:
             return super().step_into(args, actions, act_ld)
-        a = self._step_args_for(actions, act_ld)
-        call('xa_continuous_env_step', ctypes.byref(a), ctypes.byref(args), stream())
+        self._launch(self._step_args_for(actions, act_ld), args)
 
 
 def create_envs(env_name, n=1, preprocess=False, *args, mode=None, seed=55, device=None,
