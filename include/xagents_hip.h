@@ -310,8 +310,11 @@ int xa_clip_adam(float* theta, float* adam_m, float* adam_v, const float* grad, 
  * per 16 samples of a minibatch. More blocks than 32-sample tiles select 16-sample
  * tiles (the default for minibatches of <= 512 samples). Grids of < 64 blocks run
  * XCD-local when 8 x n_blocks blocks fit the device: 8 x n_blocks workgroups are
- * launched, the n_blocks that land first on one XCD do the update and keep every
- * hand-off in that XCD's L2, the rest leave at once (placement: XA_PPO_PLACE_*).
+ * launched, every 8th one (which the dispatcher places on one XCD) does the update and
+ * the rest leave at once; the update checks inside the launch that its workgroups do
+ * share an XCD, then keeps every hand-off in that XCD's L2, and hands off write-through
+ * like a spread launch if they do not (placement: XA_PPO_PLACE_*;
+ * xa_ppo_update_local tells which launch a set of arguments gets).
  * workspace: device memory, 256-byte aligned, >= xa_ppo_update_workspace_bytes(...),
  * owned by the caller, ZEROED ONCE at allocation and then reused by every launch
  * (nothing in it is reset between launches: a launch counter kept in it numbers the
@@ -329,6 +332,8 @@ int xa_clip_adam(float* theta, float* adam_m, float* adam_v, const float* grad, 
 #define XA_PPO_PLACE_SPREAD 1 /* never XCD-local */
 #define XA_PPO_PLACE_LOCAL 2  /* XCD-local when eligible, data parallel included (every
                                  rank on its own GPU) */
+#define XA_PPO_PLACE_LOCAL_WT 3 /* as XA_PPO_PLACE_LOCAL, with the in-launch check forced to
+                                   "not on one XCD": the write-through fallback (tests) */
 typedef struct XaPpoUpdateArgs {
   int obs_dim, n_actions;
   int batch, mb_size, epochs;
@@ -386,6 +391,9 @@ size_t xa_ppo_update_workspace_bytes(int obs_dim, int n_actions, int batch, int 
 size_t xa_ppo_update_dp_block_bytes(int obs_dim, int n_actions, int batch, int mb_size,
                                     int epochs, int n_blocks, int world);
 int xa_ppo_update(const XaPpoUpdateArgs* args, void* stream);
+/* 1 if xa_ppo_update runs these arguments (shape, n_blocks, dp_world, placement) as an
+ * XCD-local launch on the current device, 0 if as a spread one, -1 on bad arguments. */
+int xa_ppo_update_local(const XaPpoUpdateArgs* args);
 
 /* ------------------------------------------------------------------------- */
 /* Dense / Conv1D building blocks (CNN cfgs: xagents/dqn/models/cnn.cfg,      */

@@ -81,13 +81,14 @@ def analyse(tr, G, K):
           f'{us(np.median(c_last - b_last)):8.3f}')
     print(f'  A start skew (first -> last block at loop top) '
           f'{us(np.median(t[:, :, 0].max(0) - t[:, :, 0].min(0))):8.3f}')
-    # the launch outside the step loop: start (after the election) -> phase-0 hop done ->
-    # first loop top; last step's Adam done -> the block's end
+    # the launch outside the step loop: start (a block that stays: its launch number read,
+    # its inputs addressed) -> phase-0 hop done -> first loop top; last step's Adam done ->
+    # the block's end
     pro = tr[:G, STEPS - 1]
     start, hop = pro[:, 6], pro[:, 7]
     ent = pro[:, 5]
     print(f'  kernel entry (first) -> first / last start    {us(start.min() - ent.min()):8.3f} '
-          f'{us(start.max() - ent.min()):8.3f}  (election)')
+          f'{us(start.max() - ent.min()):8.3f}')
     print(f'  launch start skew (first -> last block)       {us(start.max() - start.min()):8.3f}')
     for a_, b_, nm in ((6, 0, 'start -> gather done'), (0, 1, 'gather -> adv sums stored'),
                        (1, 2, 'm / v + weights to LDS'), (2, 4, 'advantage totals polled'),

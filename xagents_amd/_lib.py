@@ -31,6 +31,7 @@ MLP_HIDDEN = 64
 XA_PPO_PLACE_AUTO = 0
 XA_PPO_PLACE_SPREAD = 1
 XA_PPO_PLACE_LOCAL = 2
+XA_PPO_PLACE_LOCAL_WT = 3
 XA_PPO_STATS_SLOTS = 16  # host slots of the persistent update's in-launch statistics
 
 
@@ -462,6 +463,7 @@ _SIGNATURES = {
     'xa_ppo_update_blocks': (c_int, [c_int, c_int, c_int]),
     'xa_ppo_update_workspace_bytes': (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'xa_ppo_update': (c_int, [POINTER(XaPpoUpdateArgs), c_void_p]),
+    'xa_ppo_update_local': (c_int, [POINTER(XaPpoUpdateArgs)]),
     'xa_gemm': (c_int, [POINTER(XaGemmArgs), c_void_p]),
     'xa_gemm_adam': (c_int, [POINTER(XaGemmArgs), POINTER(XaAdamApply), c_void_p]),
     'xa_conv_stack_fwd': (c_int, [POINTER(XaConvStackArgs), c_void_p]),

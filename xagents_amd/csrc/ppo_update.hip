@@ -90,6 +90,16 @@ extern "C" int xa_ppo_update(const XaPpoUpdateArgs* a, void* stream) {
   if (a->obs_dim == 8 && a->n_actions == 4) return xa_ppo_launch_8_4(a, G, K, n_mb, s);
   return xa_ppo_launch_2_3(a, G, K, n_mb, s);
 }
+
+extern "C" int xa_ppo_update_local(const XaPpoUpdateArgs* a) {
+  XA_CHECK_ARG(a != nullptr, "xa_ppo_update_local: null pointer");
+  const int cap = capacity_for(a->obs_dim, a->n_actions);
+  XA_CHECK_ARG(cap > 0, "xa_ppo_update_local: unsupported (obs_dim, n_actions) = (%d, %d)",
+               a->obs_dim, a->n_actions);
+  XA_CHECK_ARG(a->n_blocks > 0 && a->n_blocks <= cap, "xa_ppo_update_local: n_blocks %d not in "
+               "[1, resident capacity %d]", a->n_blocks, cap);
+  return use_local(a, a->n_blocks, cap) ? 1 : 0;
+}
 XA_DIAG_READER(xa_diag_read_stamps_ppo)
 #ifdef XA_TRACE
 extern "C" int xa_diag_read_trace_ppo(unsigned* host) {

@@ -59,11 +59,9 @@ constexpr int kCtlBytes = 256;              // control words at the workspace st
 // host-side skew (one process per GPU)
 constexpr uint64_t kSpinTicks = 1000000000;
 constexpr int kXcds = 8;            // MI355X: 8 XCDs, each with its own L2
-// control words: the phase-0 arrival counter ((gen + 1) G after launch gen) and the abort
-// word (the number gen + 1 of a launch that timed out), never reset; the XCD election of
-// the XCD-local mode (below) in two parity slots -- launch gen uses slot gen & 1, which
-// launch gen - 1 (of either mode) zeroed at its end
-enum { kCntStats = 0, kAbort = 1, kWin = 2 /* [2] */, kElect = 4 /* [2][kXcds] */ };
+// control words: the phase-0 arrival counter ((gen + 1) G after launch gen; unused since
+// round 6) and the abort word (the number gen + 1 of a launch that timed out), never reset
+enum { kCntStats = 0, kAbort = 1 };
 #ifndef XA_TWO_LEVEL_MIN_G  // (diagnostic A/B builds override it)
 #define XA_TWO_LEVEL_MIN_G 64
 #endif
@@ -385,13 +383,14 @@ __device__ unsigned xa_ppo_trace[256 * kTraceSteps * kTracePts];
 
 // Workspace (device memory, zeroed once by the caller at allocation; nothing in it is
 // reset between launches):
-//   ctl      control words (abort word, XCD election; word 0 unused since round 6)
+//   ctl      control words (abort word; word 0 unused since round 6)
 //   persist  the launch generation gen (the granule tags of every launch differ)
 //   rows_g   [G, PP/2] tagged pairs (8 B): the blocks' gradient rows
 //   g_g      [PP/2] tagged pairs: the reduced gradient (sized for the round-5 form, which
 //            also held per-block norm partials)
 //   adv      [K, G, 2] f64 advantage sums (phase-0 hop)
-//   cen_g    [G] granule pairs: the XCD each block runs on (two-level census)
+//   cen_g    [G] granule pairs: the XCD each block runs on (the two-level census and the
+//            XCD-local verdict)
 //   xpart_g  [kXcds, PP/2] tagged f64 pairs (16 B): per-XCD partial sums of the rows
 //            (two-level)
 // A granule is 8 bytes {32-bit value, 32-bit tag}; two of them travel in one 16-byte
@@ -566,56 +565,21 @@ struct UpdLds {
 #endif
 };
 
-// XCD-local mode: the launch has kXcds x G workgroups; the G that run on the XCD whose
-// G-th workgroup arrives first do the update (logical block ids = their arrival ranks),
-// every other workgroup leaves at once. A winner always exists once every XCD's first G
-// arrivals are resident (the host launches this mode only when kXcds G fit), and every
-// hand-off of the launch then stays inside one L2: plain stores (the lines stay in the
-// shared L2) and L1-bypassing sc1 loads, no write-through round trip to the fabric.
-// Placement decides speed, never correctness: a workgroup learns its XCD from
-// HW_REG_XCC_ID and only workgroups of the elected XCD exchange data.
-// Two halves, so that phase 0's gather runs while the election completes (speculatively:
-// nothing is stored before the winner is known). elect_rank: the workgroup's arrival rank
-// on its XCD (its logical block id if the XCD wins; >= G: leave); the G-th arrival claims the
-// winner word. Contains a __syncthreads().
-XA_DEV int elect_rank(unsigned* ctl, int G, unsigned par, int xcc, int& lds) {
-  if (threadIdx.x == 0) {
-    const unsigned r = __hip_atomic_fetch_add((gu32*)(ctl + kElect + par * kXcds + xcc), 1u,
-                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int id = r < (unsigned)G ? (int)r : -1;
-    if (r == (unsigned)G - 1u) {
-      // the G-th arrival: claim the winner word (no wait for the result here: elect_won
-      // reads it later); the claim's own result then decides without a poll
-      unsigned expect = 0u;
-      const bool mine = __hip_atomic_compare_exchange_strong(
-          (gu32*)(ctl + kWin + par), &expect, (unsigned)xcc + 1u, __ATOMIC_RELAXED,
-          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      id = mine ? id : -2 - id;  // (-2 - r: rank r of a losing XCD, decided already)
-    }
-    lds = id;
-  }
-  __syncthreads();
-  const int v = lds;
-  return v <= -2 ? -2 - v : v;
-}
-// elect_won (thread 0 only): did this XCD win? The G-th arrival knows from its claim; the
-// others poll the winner word (bounded: a timeout raises the abort word and `status`)
-XA_DEV bool elect_won(unsigned* ctl, unsigned par, int xcc, int claim, unsigned epoch,
-                      int* status) {
-  if (claim != 0) return claim > 0;
-  gu32* win_w = (gu32*)(ctl + kWin + par);
-  const uint64_t t0 = wall_clock64();
-  unsigned win;
-  while ((win = __hip_atomic_load(win_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
-    if (wall_clock64() - t0 > kSpinTicks) {
-      __hip_atomic_store((gu32*)(ctl + kAbort), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (status) __hip_atomic_store((gu32*)status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(XA_POLL_SLEEP);
-  }
-  return win == (unsigned)xcc + 1u;
-}
+// XCD-local mode: the launch has kXcds x G workgroups, and the G candidates are the
+// workgroups with blockIdx.x % kXcds == 0 (logical block id blockIdx.x / kXcds: unique under
+// any placement, no atomic); every other workgroup leaves at its first instruction without
+// touching memory. Workgroups b and b + kXcds are observed to land on one XCD
+// (MI355X_MICROARCH.md, "Workgroup dispatch"), so the candidates normally share one L2 --
+// but nothing relies on it: every candidate publishes its HW_REG_XCC_ID in a write-through
+// census granule (cen_g, the two-level census), every block polls the G granules beside the
+// phase-0 advantage sums, and all blocks read the same G values, so all reach the same
+// verdict. All equal: every later hand-off of the launch stays inside one L2 -- plain stores
+// (the lines stay in the shared L2) and L1-bypassing sc1 loads, no write-through round trip
+// to the fabric. Otherwise (or when the host forces it: loc == kLocForceWt, the test switch
+// XA_PPO_PLACE_LOCAL_WT) the launch hands off write-through like the spread mode. The
+// phase-0 sums and the census itself, the only hand-offs before the verdict, are always
+// write-through. Placement decides speed, never correctness.
+constexpr int kLocForceWt = 2;  // the kernel's loc argument: 0 spread, 1 XCD-local, 2 forced
 
 // TS = samples per tile (32; 16 when the minibatch has at most 16 tiles of 32: twice the
 // blocks, half the element-wise work per block and step); PRE = every tile input of the
@@ -641,7 +605,12 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
                                                           int n_mb_, int loc_) {
   constexpr bool FIX = BF == 3 || BF == 4;
   typedef FixShape<BF> FS;
-  const int K = FIX ? FS::K : K_, n_mb = FIX ? FS::NMB : n_mb_, loc = loc_;
+  // (the two-level-only kernels, BF 2 / 4, are never launched XCD-local: that mode's code
+  // is compiled out of them -- it cost the C2 kernel 12 more scalar spills)
+  const int K = FIX ? FS::K : K_, n_mb = FIX ? FS::NMB : n_mb_;
+  const int loc = (BF == 2 || BF == 4) ? 0 : loc_;
+  // XCD-local mode: only the candidates stay (see above)
+  if (loc && ((int)blockIdx.x & (kXcds - 1)) != 0) return;
   constexpr int RPT = Dims<OBS, A>::RPT;
   __shared__ __attribute__((aligned(16))) UpdLds<OBS, A, TS> U;
   PtLds<OBS, A, TS>& L = U.t;
@@ -650,7 +619,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   XA_STAMP_DECL
 #ifdef XA_TRACE
-  unsigned long long t_entry_;  // (diagnostic) kernel entry, before the election
+  unsigned long long t_entry_;  // (diagnostic) kernel entry
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry_)::"memory");
 #endif
 
@@ -660,18 +629,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   const unsigned gen =
       __hip_atomic_load((gu32*)ws.persist, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned epoch = gen + 1u;
-  const unsigned par = gen & 1u;
   const int xcc = xcc_id();
   const int G = FIX ? FS::G : loc ? p.n_blocks : (int)gridDim.x;
-  // XCD-local mode: the arrival rank (the block id if this XCD wins); the G-th arrival's
-  // claim result rides in U.flag's sign until elect_won (claim: +1 won, -1 lost, 0 poll)
-  int claim = 0;
-  int b = (int)blockIdx.x;
-  if (loc) {
-    b = elect_rank(ws.ctl, G, par, xcc, U.flag);
-    if (b < 0) return;
-    if (b == G - 1 && tid == 0) claim = U.flag >= 0 ? 1 : -1;
-  }
+  const int b = loc ? (int)blockIdx.x / kXcds : (int)blockIdx.x;
 #ifdef XA_TRACE
   if (tid == 0) U.trace[(kTraceSteps - 1) * kTracePts + 5] = (unsigned)t_entry_;
 #endif
@@ -691,7 +651,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   }
   XA_STAMP_BLOCK(b == 0)
   XA_STAMP(30);
-  XA_TRACE_PT(b, kTraceSteps - 1, 6);  // launch start (after the election)
+  XA_TRACE_PT(b, kTraceSteps - 1, 6);  // launch start (a candidate, its inputs addressed)
   XA_TRACE_CLK(b, 0);
   const int B = FIX ? FS::B : p.batch, MB = FIX ? FS::MB : p.mb_size;
   const uint64_t ctr = p.shuffle.rng_counter ? *p.shuffle.rng_counter : 0ull;
@@ -704,15 +664,19 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   ps.load(p.theta, wv, rv);
   ps.load(p.adam_m, mw, mr);
   ps.load(p.adam_v, vw, vr);
-  // hand-off stores: write-through across XCDs, plain inside the elected XCD's L2
-  const bool kWt = !loc;
+  // hand-off stores: write-through across XCDs (and before the XCD-local verdict below),
+  // plain once the census showed every block on one XCD's L2
+  // (the two-level-only kernels keep it a run-time value of the launch, as it always was
+  // there: their step loop then compiles as before)
+  bool kWt = (BF == 2 || BF == 4) ? loc_ == 0 : true;
 
   // ---- census: which XCD this block runs on (a granule, read after the phase-0 hop) ----
   // 16-sample tiles run only on small grids (<= 32 blocks): one level, known at compile time
   const bool two_level = BF == 2 || BF == 4 || (BF == 0 && !loc && TS == S && G >= kTwoLevelMinG);
   const __amdgpu_buffer_rsrc_t cen_r = rsrc(ws.cen_g, (uint32_t)(G * 16));
-  if (two_level && tid == 0) st_gran2(cen_r, (uint32_t)(16 * b), __uint_as_float((unsigned)xcc),
-                                      __uint_as_float((unsigned)xcc), epoch, true);
+  if ((two_level || loc) && tid == 0)
+    st_gran2(cen_r, (uint32_t)(16 * b), __uint_as_float((unsigned)xcc),
+             __uint_as_float((unsigned)xcc), epoch, true);
 
   // ---- phase 0: advantage sums of this block's samples of every minibatch; their
   // inputs into LDS when all of them fit; the Adam step size of every step ----
@@ -759,12 +723,6 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       slot[OBS + 3] = p.old_logp[idx];
     }
     __syncthreads();
-  }
-  if (loc) {
-    // stores follow: leave unless this XCD won the election
-    if (tid == 0) U.flag = elect_won(ws.ctl, par, xcc, claim, epoch, p.status) ? 1 : 0;
-    __syncthreads();
-    if (U.flag == 0) return;
   }
   XA_TRACE_PT(b, kTraceSteps - 1, 0);  // phase-0 gather done
   // preloaded inputs of <= 32 samples per step: each minibatch's sums on a 16- or 32-lane row
@@ -917,6 +875,10 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   const int CB0 = (padded(P) / 2 + G - 1) / G;
   const DpLayout dl = dp_layout(G, W, K, CB0);
   bool dp_bad = false;  // a phase-0 poll (or the DP exchange) timed out / aborted
+  // XCD-local mode: thread t < G (wave 0: G < 64) reads candidate t's census granule; the
+  // first load is issued here and returns under the advantage poll below
+  f32x4v cen_v = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (loc && tid < G) cen_v = __builtin_amdgcn_raw_buffer_load_b128(cen_r, (uint32_t)(16 * tid), 0, kAuxSc1);
   {
     // the blocks' per-minibatch advantage sums: wave w sums minibatches w, w + 4, ...; it
     // issues the 16-B {s1, s2} sc1 loads of up to kAB (minibatch, block) pairs at once (one
@@ -958,6 +920,21 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     }
     // (the wave reads back only its own LDS words, in issue order)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  }
+  if (loc && w == 0) {
+    // the verdict: every candidate on this block's XCD (all blocks read the same G values)
+    bool other = false;
+    if (tid < G) {
+      if (!gran_ok(cen_v, epoch)) {
+        const uint32_t off[1] = {(uint32_t)(16 * tid)};
+        f32x4v v[1];
+        dp_bad = !poll_gran<1>(cen_r, off, 1, epoch, v, ws.ctl, epoch, p.status) || dp_bad;
+        cen_v = v[0];
+      }
+      other = (int)__float_as_uint(cen_v[0]) != xcc;
+    }
+    const bool together = __ballot(other) == 0ull;
+    if (lane == 0) U.flag = together && loc != kLocForceWt ? 1 : 0;
   }
   XA_TRACE_PT(b, kTraceSteps - 1, 4);  // the advantage totals summed
   for (int k = w; DP && k < K; k += 4) {
@@ -1014,6 +991,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   }
 
   if (__syncthreads_or(dp_bad)) return;
+  // (wave 0 wrote the flag before the barrier; readfirstlane keeps kWt a scalar, so the
+  // step loop's store forms stay uniform branches)
+  if (loc) kWt = __builtin_amdgcn_readfirstlane(U.flag) == 0;
   XA_TRACE_PT(b, kTraceSteps - 1, 3);  // the minibatch statistics in LDS
 
   // per-sample inputs of the next tile (threads < TS), fetched one tile ahead -- across
@@ -1601,15 +1581,6 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   }
   XA_TRACE_CLK(b, 1);
   XA_TRACE_FLUSH(b);
-  if (b == 0 && tid == 0) {
-    // zero the election slot of the next launch (this launch's slot is par; launch
-    // gen + 1 uses par ^ 1, which launch gen - 1 used and nothing touches now)
-    for (int x = 0; x < kXcds; ++x)
-      __hip_atomic_store((gu32*)(ws.ctl + kElect + (par ^ 1u) * kXcds + x), 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((gu32*)(ws.ctl + kWin + (par ^ 1u)), 0u, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
   // theta / m / v out: every block holds the same final values, so block b stores the
   // slices of threads tid = b, b + G, ... (all blocks share the stores instead of block 0
   // issuing every one of them at the launch's end); block 0 alone the counters
@@ -1695,17 +1666,20 @@ int capacity() {
 // (xa_ppo_update_blocks picks that for minibatches of <= 16 such tiles), else 32
 int tile_samples(int mb_size, int G) { return G > (mb_size + S - 1) / S ? 16 : S; }
 
-// XCD-local mode (elect_local): small grids (one level, G <= 32 at one block per CU), when
-// kXcds G blocks are co-resident; data-parallel launches only when every rank owns its GPU
-// (ranks sharing one GPU could strand each other's elections). XA_PPO_LOCAL=0 disables it.
+// XCD-local mode: small grids (one level, G <= 32 at one block per CU), when kXcds G blocks
+// are co-resident; data-parallel launches only when the caller asks (every rank on its own
+// GPU: ranks sharing one would spread each other's candidates). XA_PPO_LOCAL=0 disables it.
 bool use_local(const XaPpoUpdateArgs* a, int G, int cap) {
   static const int env = [] {
     const char* e = getenv("XA_PPO_LOCAL");
     return e && e[0] == '0' ? 0 : 1;
   }();
   if (!env || a->placement == XA_PPO_PLACE_SPREAD) return false;
-  if (a->dp_world > 1 && a->placement != XA_PPO_PLACE_LOCAL) return false;
-  return G < kTwoLevelMinG && (long)G * kXcds <= (long)cap;
+  if (a->dp_world > 1 && a->placement != XA_PPO_PLACE_LOCAL &&
+      a->placement != XA_PPO_PLACE_LOCAL_WT)
+    return false;
+  // (G < 64: one wave reads the census)
+  return G < kTwoLevelMinG && G < 64 && (long)G * kXcds <= (long)cap;
 }
 
 // every block's phase-B slice (pair columns [b CB, (b + 1) CB) of NP2) takes the kernel's
@@ -1729,7 +1703,7 @@ void launch_ts(const XaPpoUpdateArgs* a, int G, bool dp, bool loc, const Ws& ws,
   const int n_tiles_max = (min(a->mb_size, a->batch) + TS - 1) / TS;
   const int TPB = (n_tiles_max + G - 1) / G;
   const bool pre = K * TPB * TS <= pre_max<OBS>();
-  const int l = loc ? 1 : 0;
+  const int l = !loc ? 0 : a->placement == XA_PPO_PLACE_LOCAL_WT ? kLocForceWt : 1;
   // the fixed-shape instantiations (BF 3 / 4) for exactly their shape; XA_PPO_FIXED_SHAPE=0
   // forces the generic ones (A/B)
   static const bool fix_on = [] {

@@ -216,13 +216,14 @@ class PPO(A2C):
         u.bump_counter = int(bool(self.shuffle.rng_counter))
         u.dp_world, u.dp_rank = 1, 0
         # XCD-local placement of small grids (xa_ppo_update): automatic in one process; data
-        # parallel only when every rank owns its GPU (ranks sharing one could strand each
-        # other's XCD elections). XA_PPO_PLACE=spread|local overrides.
-        # The election needs G free CU slots on ONE XCD (at G = 32 with one block per CU:
-        # all 8 x 32 CUs idle), so it assumes the update owns the GPU while it runs: a
-        # kernel overlapping it on another stream could hold a CU on every XCD and stall
-        # every spinning block until the abort. The opt-in side-stream statistics copy
-        # (XA_STATS_SIDE_STREAM=1) can overlap the update, so it forces the spread grid.
+        # parallel only when every rank owns its GPU (ranks sharing one would spread each
+        # other's workgroups over the XCDs). XA_PPO_PLACE=spread|local overrides.
+        # The XCD-local launch puts its G workgroups on ONE XCD (at G = 32 with one block
+        # per CU: all of that XCD's CUs), so it assumes the update owns the GPU while it
+        # runs: a kernel overlapping it on another stream could hold CUs there and keep
+        # the spinning blocks waiting for the ones not yet resident. The opt-in side-stream
+        # statistics copy (XA_STATS_SIDE_STREAM=1) can overlap the update, so it forces the
+        # spread grid.
         place = os.environ.get('XA_PPO_PLACE', 'auto')
         if getattr(self, 'stats_side_stream', False) and place != 'local':
             place = 'spread'
