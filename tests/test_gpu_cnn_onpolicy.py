@@ -80,39 +80,11 @@ def _ppo(device, n=4, t=8, kind='ppo'):
     return A2C(envs, model, n_steps=t, seed=8, quiet=True)
 
 
-def _heads_grad_f64(logits, v, act, oldlp, oldv, ret, kind, clip=0.1, ent_coef=0.01,
-                    v_coef=0.5, eps=1e-8):
-    import oracle as OR
-    n, A = logits.shape
-    lsm = OR.log_softmax(logits)
-    p = np.exp(lsm)
-    logp = lsm[np.arange(n), act]
-    H = -(p * lsm).sum(-1)
-    onehot = np.eye(A)[act]
-    if kind == 'ppo':
-        adv = ret - oldv
-        adv = (adv - adv.mean()) / (adv.std() + eps)
-        ratio = np.exp(logp - oldlp)
-        pg1, pg2 = -adv * ratio, -adv * np.clip(ratio, 1 - clip, 1 + clip)
-        r_in = (ratio >= 1 - clip) & (ratio <= 1 + clip)
-        dlogp = np.where((pg1 >= pg2) | r_in, -adv * ratio, 0.0) / n
-        dvo = v - oldv
-        vclip = oldv + np.clip(dvo, -clip, clip)
-        vl1, vl2 = (v - ret) ** 2, (vclip - ret) ** 2
-        v_in = (dvo >= -clip) & (dvo <= clip)
-        dv = v_coef * 0.5 * np.where(vl1 >= vl2, 2 * (v - ret),
-                                     np.where(v_in, 2 * (vclip - ret), 0.0)) / n
-    else:
-        dlogp = -(ret - oldv) / n
-        dv = v_coef * 2 * (v - ret) / n
-    dz = dlogp[:, None] * (onehot - p) + (ent_coef / n) * p * (lsm + H[:, None])
-    return dz, dv
-
-
 @pytest.mark.parametrize('kind', ['ppo', 'a2c'])
 def test_cnn_actor_critic_train_step_vs_f64(device, kind):
     import nets_f64 as O
     import oracle as OR
+    from heads_ref import heads_f64
     agent = _ppo(device, kind=kind)
     model = agent.model
     th0 = model.theta.cpu().numpy().astype(np.float64)
@@ -135,7 +107,7 @@ def test_cnn_actor_critic_train_step_vs_f64(device, kind):
     np.testing.assert_allclose(oldlp, lp_ref, rtol=1e-4, atol=1e-5)
     agent._executor_update()
     torch.cuda.synchronize()
-    dz, dv = _heads_grad_f64(logits, v, act, oldlp, oldv, ret, kind)
+    dz, dv, _ = heads_f64(logits, v, act, oldlp, oldv, ret, kind)
     g = O.backward(model.layers, th0, x64, outs,
                    {model.outputs[0]: dz, model.outputs[1]: dv[:, None]})
     g = OR.clip_by_global_norm_f64(g, 0.5)[0]

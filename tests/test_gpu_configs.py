@@ -119,7 +119,7 @@ def test_c4_ppo_cnn_128_env_shard(device):
     pre-activations ~0 and the cancelling f32 sums of the conv weight gradients."""
     import nets_torch64 as OT
     import oracle as OR
-    from test_gpu_cnn_onpolicy import _heads_grad_f64
+    from heads_ref import heads_f64
     from xagents_amd import PPO
     from xagents_amd.envs import create_envs
     from xagents_amd.utils.common import create_model
@@ -162,9 +162,9 @@ def test_c4_ppo_cnn_128_env_shard(device):
         thg = th.double().requires_grad_(True)
         _, outs = OT.forward(model.layers, thg, x, model.input_shape)
         logits, val = outs[o_logits], outs[o_value][:, 0]
-        dz, dv = _heads_grad_f64(logits.detach().cpu().numpy(), val.detach().cpu().numpy(),
-                                 act_all[idx].cpu().numpy(), logp_all[idx].cpu().numpy(),
-                                 val_all[idx].cpu().numpy(), ret_all[idx].cpu().numpy(), 'ppo')
+        dz, dv, _ = heads_f64(logits.detach().cpu().numpy(), val.detach().cpu().numpy(),
+                               act_all[idx].cpu().numpy(), logp_all[idx].cpu().numpy(),
+                               val_all[idx].cpu().numpy(), ret_all[idx].cpu().numpy(), 'ppo')
         g, = torch.autograd.grad([logits, outs[o_value]], [thg], grad_outputs=[
             torch.from_numpy(dz).to(device), torch.from_numpy(dv[:, None]).to(device)])
         del outs, logits, val, thg

@@ -78,45 +78,6 @@ def test_diag_gaussian_kernel(device):
                 assert abs(np.corrcoef(y[:, j], y[:, jj])[0, 1]) < 0.03, (j, jj)
 
 
-def _heads_f64(out_a, v, act, oldlp, oldv, ret, kind, dist, clip=0.1, ent_coef=0.01,
-               v_coef=0.5, eps=1e-8):
-    """d loss / d actor output and d loss / d value (ppo/agent.py:96-137, a2c 190-218)
-    for MultivariateNormalDiag(loc) or Categorical(probs = softmax(z))."""
-    import oracle as OR
-    n = out_a.shape[0]
-    if dist == 'gauss':
-        d = out_a.shape[1]
-        diff = act - out_a
-        logp = -0.5 * (diff ** 2).sum(1) - 0.5 * d * LOG2PI
-        dlogp_dz = diff
-        dH = np.zeros_like(out_a)
-    else:
-        lsm = OR.log_softmax(out_a)
-        p = np.exp(lsm)
-        logp = np.log(p[np.arange(n), act.astype(int)])  # Categorical(probs).log_prob
-        H = -(p * lsm).sum(-1)
-        dlogp_dz = np.eye(out_a.shape[1])[act.astype(int)] - p
-        dH = -p * (lsm + H[:, None])  # dH/dz
-    if kind == 'ppo':
-        adv = ret - oldv
-        adv = (adv - adv.mean()) / (adv.std() + eps)
-        ratio = np.exp(logp - oldlp)
-        pg1, pg2 = -adv * ratio, -adv * np.clip(ratio, 1 - clip, 1 + clip)
-        r_in = (ratio >= 1 - clip) & (ratio <= 1 + clip)
-        dlogp = np.where((pg1 >= pg2) | r_in, -adv * ratio, 0.0) / n
-        dvo = v - oldv
-        vclip = oldv + np.clip(dvo, -clip, clip)
-        vl1, vl2 = (v - ret) ** 2, (vclip - ret) ** 2
-        v_in = (dvo >= -clip) & (dvo <= clip)
-        dv = v_coef * 0.5 * np.where(vl1 >= vl2, 2 * (v - ret),
-                                     np.where(v_in, 2 * (vclip - ret), 0.0)) / n
-    else:
-        dlogp = -(ret - oldv) / n
-        dv = v_coef * 2 * (v - ret) / n
-    dz = dlogp[:, None] * dlogp_dz - (ent_coef / n) * dH
-    return dz, dv, logp
-
-
 def _softmax_cfg(tmp_path):
     src = ROOT / 'xagents_amd' / 'ppo' / 'models' / 'ann-actor-critic.cfg'
     text = src.read_text().replace('[dense-2]\n', '[dense-2]\nactivation=softmax\n')
@@ -129,6 +90,7 @@ def _softmax_cfg(tmp_path):
                                        ('a2c', 'softmax')])
 def test_policy_distribution_train_step_vs_f64(device, tmp_path, kind, dist):
     import nets_f64 as O
+    from heads_ref import heads_f64
     from xagents_amd import A2C, PPO
     from xagents_amd.envs import create_envs
     from xagents_amd.utils.common import create_model
@@ -161,7 +123,7 @@ def test_policy_distribution_train_step_vs_f64(device, tmp_path, kind, dist):
     x64, outs = O.forward(model.layers, th0, x, model.input_shape)
     za, v = outs[model.outputs[0]], outs[model.outputs[1]][:, 0]
     np.testing.assert_allclose(oldv, v, rtol=1e-4, atol=1e-5)
-    _, _, lp_ref = _heads_f64(za, v, act, oldlp, oldv, ret, kind, dist)
+    _, _, lp_ref = heads_f64(za, v, act, oldlp, oldv, ret, kind, dist)
     np.testing.assert_allclose(oldlp, lp_ref, rtol=1e-4, atol=1e-4)
     ent = _np(agent.b_ent).reshape(-1)
     if dist == 'gauss':
@@ -171,7 +133,7 @@ def test_policy_distribution_train_step_vs_f64(device, tmp_path, kind, dist):
     slots = agent._slots_flat[:agent.mb].cpu().numpy()
     x64, outs = O.forward(model.layers, th0, x[slots], model.input_shape)
     za, v = outs[model.outputs[0]], outs[model.outputs[1]][:, 0]
-    dz, dv, _ = _heads_f64(za, v, act[slots], oldlp[slots], oldv[slots], ret[slots], kind, dist)
+    dz, dv, _ = heads_f64(za, v, act[slots], oldlp[slots], oldv[slots], ret[slots], kind, dist)
     assert _rel(_np(agent.dlogits[:agent.mb]), dz) < 1e-4
     assert _rel(_np(agent.dvalue[:agent.mb, 0]), dv) < 1e-4
     g = O.backward(model.layers, th0, x64, outs, {model.outputs[0]: dz, model.outputs[1]: dv[:, None]})

@@ -267,7 +267,8 @@ def test_mse_grad_kernel_vs_f64(device):
 def test_cnn_head_raw_gradient_losses_and_chained_updates(device, kind):
     import nets_f64 as O
     import oracle as OR
-    from test_gpu_cnn_onpolicy import _heads_grad_f64, _ppo
+    from heads_ref import heads_f64
+    from test_gpu_cnn_onpolicy import _ppo
     agent = _ppo(device, n=4, t=8, kind=kind)
     model = agent.model
     N, T = agent.n_envs, agent.n_steps
@@ -287,7 +288,7 @@ def test_cnn_head_raw_gradient_losses_and_chained_updates(device, kind):
         xs, a_, lp_, v_, r_ = x[slots], act[slots], oldlp[slots], oldv[slots], ret[slots]
         x64, outs = O.forward(model.layers, before[0], xs, model.input_shape)
         logits, v = outs[model.outputs[0]], outs[model.outputs[1]][:, 0]
-        dz, dv = _heads_grad_f64(logits, v, a_, lp_, v_, r_, kind)
+        dz, dv, _ = heads_f64(logits, v, a_, lp_, v_, r_, kind)
         assert _rel(_np(agent.dlogits[:n]), dz) < 1e-4, f'step {k}: dlogits'
         assert _rel(_np(agent.dvalue[:n, 0]), dv) < 1e-4, f'step {k}: dvalue'
         lsm = OR.log_softmax(logits)

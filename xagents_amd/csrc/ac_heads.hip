@@ -8,11 +8,15 @@
 //   * xa_ac_head_grad: the PPO / A2C loss of a minibatch and its gradient w.r.t. the
 //     logits (or the Gaussian mean) and the value head (PPO.update_gradients ppo/agent.py:96-137 with the
 //     per-minibatch advantage normalisation of run_ppo_epochs 180-183; A2C.train_step
-//     a2c/agent.py:190-218), TF tie semantics as in ac_update.hip.
+//     a2c/agent.py:190-218); the loss terms and their TF tie rules are ac_loss.hpp's, shared
+//     with the tile kernels.
 #include "../../include/xagents_hip.h"
+#include "ac_loss.hpp"
 #include "xa_common.hpp"
 
 namespace {
+
+using xa_ac::ac_loss_terms;
 
 constexpr int kMaxA = 64;
 constexpr float kLog2Pi = 1.83787706640934548f;  // log(2 pi)
@@ -186,24 +190,11 @@ __global__ __launch_bounds__(1024) void ac_head_grad_kernel(XaHeadGradArgs p) {
     if (ppo) {
       const float adv = (adv_raw - adv_mean) / (adv_std + p.adv_eps);
       const float ratio = xa_expf(logp - p.old_logp[i]);
-      const float c = p.clip_norm;
-      const float pg1 = -adv * ratio;
-      const float pg2 = -adv * fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-      pg = fmaxf(pg1, pg2);
-      const bool r_in = ratio >= 1.0f - c && ratio <= 1.0f + c;
-      dlogp = (pg1 >= pg2 || r_in) ? (sc * -adv) * ratio : 0.0f;
-      const float dvo = v - oldv;
-      const float vclip = oldv + fminf(fmaxf(dvo, -c), c);
-      const float vl1 = (v - R) * (v - R), vl2 = (vclip - R) * (vclip - R);
-      vl = fmaxf(vl1, vl2);
-      const float kv = sc * p.value_coef * 0.5f * 2.0f;
-      if (vl1 >= vl2) dv = kv * (v - R);
-      else dv = (dvo >= -c && dvo <= c) ? kv * (vclip - R) : 0.0f;
-    } else {
-      pg = -(adv_raw * logp);
-      dlogp = -sc * adv_raw;
-      vl = (v - R) * (v - R);
-      dv = sc * p.value_coef * 2.0f * (v - R);
+      ac_loss_terms(true, adv, ratio, logp, v, oldv, R, p.clip_norm, sc, p.value_coef, pg,
+                    dlogp, vl, dv);
+    } else {  // A2C: the raw advantage, no ratio, no clip
+      ac_loss_terms(false, adv_raw, 0.0f, logp, v, oldv, R, 0.0f, sc, p.value_coef, pg, dlogp,
+                    vl, dv);
     }
     float* dz = p.dlogits + (int64_t)i * A;
     for (int j = 0; j < A; ++j) dz[j] = dlogp * (a[j] - z[j]);
@@ -239,24 +230,11 @@ __global__ __launch_bounds__(1024) void ac_head_grad_kernel(XaHeadGradArgs p) {
     if (ppo) {
       const float adv = (adv_raw - adv_mean) / (adv_std + p.adv_eps);
       const float ratio = xa_expf(logp - p.old_logp[i]);
-      const float c = p.clip_norm;
-      const float pg1 = -adv * ratio;
-      const float pg2 = -adv * fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-      pg = fmaxf(pg1, pg2);
-      const bool r_in = ratio >= 1.0f - c && ratio <= 1.0f + c;
-      dlogp = (pg1 >= pg2 || r_in) ? (sc * -adv) * ratio : 0.0f;
-      const float dvo = v - oldv;
-      const float vclip = oldv + fminf(fmaxf(dvo, -c), c);
-      const float vl1 = (v - R) * (v - R), vl2 = (vclip - R) * (vclip - R);
-      vl = fmaxf(vl1, vl2);
-      const float kv = sc * p.value_coef * 0.5f * 2.0f;
-      if (vl1 >= vl2) dv = kv * (v - R);
-      else dv = (dvo >= -c && dvo <= c) ? kv * (vclip - R) : 0.0f;
-    } else {
-      pg = -(adv_raw * logp);
-      dlogp = -sc * adv_raw;
-      vl = (v - R) * (v - R);
-      dv = sc * p.value_coef * 2.0f * (v - R);
+      ac_loss_terms(true, adv, ratio, logp, v, oldv, R, p.clip_norm, sc, p.value_coef, pg,
+                    dlogp, vl, dv);
+    } else {  // A2C: the raw advantage, no ratio, no clip
+      ac_loss_terms(false, adv_raw, 0.0f, logp, v, oldv, R, 0.0f, sc, p.value_coef, pg, dlogp,
+                    vl, dv);
     }
     const float ec = sc * p.entropy_coef;
     float* dz = p.dlogits + (int64_t)i * A;

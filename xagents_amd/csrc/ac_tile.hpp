@@ -7,7 +7,8 @@
 // Tile schedule (256 threads = 4 waves, S = 32 samples):
 //   H1 = tanh(X W1 + b1)                (VALU, K = obs)
 //   Z2 = H1 W2                          (MFMA f32 16x16x4, K = 64)
-//   heads + loss + dL/dz                (8 lanes per sample, xor shuffles)
+//   heads + loss + dL/dz                (8 lanes per sample, xor shuffles; the loss terms
+//                                        and their tie rules: ac_loss.hpp)
 //   dA2 = (dZ W34^T) * (1 - H2^2)       (VALU, K = A + 1)
 //   dW2 += H1^T dA2 ; dH1 = dA2 W2^T    (MFMA f32 16x16x4, K = 32 / 64)
 //   dW1 += X^T dA1                      (VALU, K = 32)
@@ -23,6 +24,7 @@
 #include <stddef.h>
 
 #include "../../include/xagents_hip.h"
+#include "ac_loss.hpp"
 #include "xa_adam.hpp"
 #include "xa_common.hpp"
 
@@ -47,20 +49,28 @@ XA_DEV float frcp(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   return fmaf(fmaf(-x, r, 1.0f), r, r);  // one Newton step
 }
-XA_DEV float ftanh(float x) {
-  const float c = 7.90531110763549805f;
-  const float xc = fminf(fmaxf(x, -c), c);
-  const float x2 = xc * xc;
-  float p = fmaf(x2, -2.76076847742355e-16f, 2.00018790482477e-13f);
-  p = fmaf(x2, p, -8.60467152213735e-11f);
-  p = fmaf(x2, p, 5.12229709037114e-08f);
-  p = fmaf(x2, p, 1.48572235717979e-05f);
-  p = fmaf(x2, p, 6.37261928875436e-04f);
-  p = fmaf(x2, p, 4.89352455891786e-03f);
+// xa_tanhf's rational tanh(xc) = xc P(x2) / Q(x2) on the clamped argument, x2 = xc^2: the
+// numerator p and the denominator q, on one value (V = float) or a packed pair (xa_f2)
+constexpr float kTanhClamp = 7.90531110763549805f;
+template <class V>
+XA_DEV void tanh_pq(V xc, V x2, V& p, V& q) {
+  auto k = [](float v) { return (V)(v); };
+  auto fma = [](V a, V b, V c) { return __builtin_elementwise_fma(a, b, c); };
+  p = fma(x2, k(-2.76076847742355e-16f), k(2.00018790482477e-13f));
+  p = fma(x2, p, k(-8.60467152213735e-11f));
+  p = fma(x2, p, k(5.12229709037114e-08f));
+  p = fma(x2, p, k(1.48572235717979e-05f));
+  p = fma(x2, p, k(6.37261928875436e-04f));
+  p = fma(x2, p, k(4.89352455891786e-03f));
   p = xc * p;
-  float q = fmaf(x2, 1.19825839466702e-06f, 1.18534705686654e-04f);
-  q = fmaf(x2, q, 2.26843463243900e-03f);
-  q = fmaf(x2, q, 4.89352518554385e-03f);
+  q = fma(x2, k(1.19825839466702e-06f), k(1.18534705686654e-04f));
+  q = fma(x2, q, k(2.26843463243900e-03f));
+  q = fma(x2, q, k(4.89352518554385e-03f));
+}
+XA_DEV float ftanh(float x) {
+  const float xc = fminf(fmaxf(x, -kTanhClamp), kTanhClamp);
+  float p, q;
+  tanh_pq(xc, xc * xc, p, q);
   return p * frcp(q);
 }
 
@@ -142,6 +152,25 @@ struct LossCfg {
   float adv_rstd;  // 1 / (adv_std + adv_eps), set with adv_std
 };
 
+// Flat parameter index e (outside W2; -1: none) -> its float offset inside the LDS struct
+// T of a tile kernel (the sW1 / sb1 / sb2 / sW34 / sb34 weight tiles), -1 for none.
+template <class T, int OBS, int A>
+XA_DEV int lds_offset_of(int e) {
+  constexpr int AH = A + 1;
+  const Offs o = offs(OBS, A);
+  if (e < 0) return -1;
+  if (e < o.b1) return (int)(offsetof(T, sW1) / 4) + e;
+  if (e < o.w2) return (int)(offsetof(T, sb1) / 4) + (e - o.b1);
+  if (e < o.w3) return (int)(offsetof(T, sb2) / 4) + (e - o.b2);
+  if (e < o.b3) {
+    const int jj = (e - o.w3) / A, a = (e - o.w3) - jj * A;
+    return (int)(offsetof(T, sW34) / 4) + jj * AH + a;
+  }
+  if (e < o.w4) return (int)(offsetof(T, sb34) / 4) + (e - o.b3);
+  if (e < o.b4) return (int)(offsetof(T, sW34) / 4) + (e - o.w4) * AH + A;
+  return (int)(offsetof(T, sb34) / 4) + A;
+}
+
 // A thread's slice of the flat parameter vector (see the file comment).
 template <int OBS, int A>
 struct ParamSlice {
@@ -150,8 +179,6 @@ struct ParamSlice {
   int ri[RPT];    // flat index of rest value q, -1 past the end
   int rdst[RPT];  // its float offset inside TileLds (the LDS weight tiles), -1 past the end
   XA_DEV void init(int tid) {
-    typedef TileLds<OBS, A> T;
-    constexpr int AH = A + 1;
     const Offs o = offs(OBS, A);
     k0 = 4 * (tid >> 4);
     j0 = 4 * (tid & 15);
@@ -160,18 +187,7 @@ struct ParamSlice {
       const int r = tid + 256 * q;
       const int e = r < NREST ? (r < o.w2 ? r : r + H * H) : -1;
       ri[q] = e;
-      int d = -1;
-      if (e < 0) d = -1;
-      else if (e < o.b1) d = (int)(offsetof(T, sW1) / 4) + e;
-      else if (e < o.w2) d = (int)(offsetof(T, sb1) / 4) + (e - o.b1);
-      else if (e < o.w3) d = (int)(offsetof(T, sb2) / 4) + (e - o.b2);
-      else if (e < o.b3) {
-        const int jj = (e - o.w3) / A, a = (e - o.w3) - jj * A;
-        d = (int)(offsetof(T, sW34) / 4) + jj * AH + a;
-      } else if (e < o.w4) d = (int)(offsetof(T, sb34) / 4) + (e - o.b3);
-      else if (e < o.b4) d = (int)(offsetof(T, sW34) / 4) + (e - o.w4) * AH + A;
-      else d = (int)(offsetof(T, sb34) / 4) + A;
-      rdst[q] = d;
+      rdst[q] = lds_offset_of<TileLds<OBS, A>, OBS, A>(e);
     }
   }
   XA_DEV size_t w2_off(int rr) const { return (size_t)offs(OBS, A).w2 + (k0 + rr) * H + j0; }
@@ -357,34 +373,16 @@ XA_DEV void tile_compute(TileLds<OBS, A>& L, TileAcc<OBS, A>& acc, const LossCfg
         const float oldv = in.oldv(s);
         const float adv_raw = R - oldv;
         const float sc = cfg.loss_scale;
-        float dlogp, dv, pg, vl;
+        float pg, dlogp, vl, dv;
         if (cfg.is_ppo) {
           const float adv =
               cfg.has_adv_in ? in.advin(s) : (adv_raw - cfg.adv_mean) * cfg.adv_rstd;
           const float ratio = fexp(logp - in.oldlp(s));
-          const float c = cfg.clip_norm;
-          const float pg1 = -adv * ratio;
-          const float pg2 = -adv * fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-          pg = fmaxf(pg1, pg2);
-          // tf.maximum routes the gradient to its first input when x >= y; the
-          // second input's gradient passes tf.clip_by_value only inside [lo, hi]
-          const bool r_in = ratio >= 1.0f - c && ratio <= 1.0f + c;
-          dlogp = (pg1 >= pg2 || r_in) ? (sc * -adv) * ratio : 0.0f;
-          const float dvo = v - oldv;
-          const float vclip = oldv + fminf(fmaxf(dvo, -c), c);
-          const float vl1 = (v - R) * (v - R);
-          const float vl2 = (vclip - R) * (vclip - R);
-          vl = fmaxf(vl1, vl2);
-          // rounding can make oldv + (v - oldv) != v inside the clip range: the
-          // clipped branch then still carries the gradient 2 (v_clip - R)
-          const float kv = sc * cfg.value_coef * 0.5f * 2.0f;
-          if (vl1 >= vl2) dv = kv * (v - R);
-          else dv = (dvo >= -c && dvo <= c) ? kv * (vclip - R) : 0.0f;
-        } else {
-          pg = -(adv_raw * logp);
-          dlogp = -sc * adv_raw;
-          vl = (v - R) * (v - R);
-          dv = sc * cfg.value_coef * 2.0f * (v - R);
+          ac_loss_terms(true, adv, ratio, logp, v, oldv, R, cfg.clip_norm, sc, cfg.value_coef,
+                        pg, dlogp, vl, dv);
+        } else {  // A2C: the raw advantage, no ratio, no clip
+          ac_loss_terms(false, adv_raw, 0.0f, logp, v, oldv, R, 0.0f, sc, cfg.value_coef, pg,
+                        dlogp, vl, dv);
         }
         const float ec = sc * cfg.entropy_coef;
 #pragma unroll

@@ -13,7 +13,8 @@
 //      H2 = tanh(Z2 + b2) in registers;          (thread ownership below)
 //      head partials over the wave's 16 units    DPP row sums -> LDS            | barrier
 //   3  logits / value (4 wave partials + b34), the clipped PPO loss and dL/dz per sample,
-//      each lane for its own samples (no broadcast); dA2 = (dz W34^T)(1 - H2^2) in
+//      each lane for its own samples (no broadcast; the loss terms and their tie rules
+//      are ac_loss.hpp's); dA2 = (dz W34^T)(1 - H2^2) in
 //      registers and LDS; head / b2 gradients;
 //      dW2[:, i] += H1^T dA2                     MFMA, B operand = the lane's dA2   | barrier
 //   4  dH1[s][i] = dA2[s] W2[i, :]^T             MFMA (A: dA2 from LDS, B: W2 row i,
@@ -107,9 +108,6 @@ struct PSlice {
     }
   }
   XA_DEV void init(int tid) {
-    typedef PtLds<OBS, A, TS> T;
-    constexpr int AH = A + 1;
-    const Offs o = offs(OBS, A);
     const int w = tid >> 6, lane = tid & 63;
     col = 16 * w + (lane & 15);
     row0 = 16 * (lane >> 4);
@@ -118,18 +116,7 @@ struct PSlice {
       const int e = rest_of(tid, q);
       ri[q] = e;
       rx[q] = e >= 0 ? exchange_of_rest<OBS, A>(e) : -1;
-      int d = -1;
-      if (e < 0) d = -1;
-      else if (e < o.b1) d = (int)(offsetof(T, sW1) / 4) + e;
-      else if (e < o.w2) d = (int)(offsetof(T, sb1) / 4) + (e - o.b1);
-      else if (e < o.w3) d = (int)(offsetof(T, sb2) / 4) + (e - o.b2);
-      else if (e < o.b3) {
-        const int jj = (e - o.w3) / A, a = (e - o.w3) - jj * A;
-        d = (int)(offsetof(T, sW34) / 4) + jj * AH + a;
-      } else if (e < o.w4) d = (int)(offsetof(T, sb34) / 4) + (e - o.b3);
-      else if (e < o.b4) d = (int)(offsetof(T, sW34) / 4) + (e - o.w4) * AH + A;
-      else d = (int)(offsetof(T, sb34) / 4) + A;
-      rdst[q] = d;
+      rdst[q] = lds_offset_of<PtLds<OBS, A, TS>, OBS, A>(e);
     }
   }
   XA_DEV int w2_canon(int kk) const { return offs(OBS, A).w2 + (row0 + kk) * H + col; }
@@ -180,22 +167,12 @@ struct PtAcc {
 
 // ftanh (ac_tile.hpp) on two values at once: packed f32 polynomial and Newton step
 XA_DEV xa_f2 ftanh2(xa_f2 x) {
-  const float c = 7.90531110763549805f;
+  const float c = kTanhClamp;
   const xa_f2 xc = {fminf(fmaxf(x.x, -c), c), fminf(fmaxf(x.y, -c), c)};
-  const xa_f2 x2 = xc * xc;
-  auto k2 = [](float v) { return xa_f2{v, v}; };
-  xa_f2 p = xa_fma2(x2, k2(-2.76076847742355e-16f), k2(2.00018790482477e-13f));
-  p = xa_fma2(x2, p, k2(-8.60467152213735e-11f));
-  p = xa_fma2(x2, p, k2(5.12229709037114e-08f));
-  p = xa_fma2(x2, p, k2(1.48572235717979e-05f));
-  p = xa_fma2(x2, p, k2(6.37261928875436e-04f));
-  p = xa_fma2(x2, p, k2(4.89352455891786e-03f));
-  p = xc * p;
-  xa_f2 q = xa_fma2(x2, k2(1.19825839466702e-06f), k2(1.18534705686654e-04f));
-  q = xa_fma2(x2, q, k2(2.26843463243900e-03f));
-  q = xa_fma2(x2, q, k2(4.89352518554385e-03f));
+  xa_f2 p, q;
+  tanh_pq(xc, xc * xc, p, q);
   const xa_f2 r = {__builtin_amdgcn_rcpf(q.x), __builtin_amdgcn_rcpf(q.y)};
-  const xa_f2 rn = xa_fma2(xa_fma2(-q, r, k2(1.0f)), r, r);  // one Newton step
+  const xa_f2 rn = xa_fma2(xa_fma2(-q, r, xa_f2{1.0f, 1.0f}), r, r);  // one Newton step
   return p * rn;
 }
 
@@ -390,25 +367,10 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
       const float v = z[A], R_ = rs[OBS + 1], oldv = rs[OBS + 2];
       const float adv = ((R_ - oldv) - cfg.adv_mean) * cfg.adv_rstd;
       const float ratio = fexp(logp - rs[OBS + 3]);
-      const float c = cfg.clip_norm, sc = cfg.loss_scale;
-      const float pg1 = -adv * ratio;
-      const float pg2 = -adv * fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-      const float pg = fmaxf(pg1, pg2);
-      // tf.maximum routes the gradient to its first input when x >= y; the second
-      // input's gradient passes tf.clip_by_value only inside [lo, hi]
-      const bool r_in = ratio >= 1.0f - c && ratio <= 1.0f + c;
-      const float dlogp = (pg1 >= pg2 || r_in) ? (sc * -adv) * ratio : 0.0f;
-      const float dvo = v - oldv;
-      const float vclip = oldv + fminf(fmaxf(dvo, -c), c);
-      const float vl1 = (v - R_) * (v - R_);
-      const float vl2 = (vclip - R_) * (vclip - R_);
-      const float vl = fmaxf(vl1, vl2);
-      // rounding can make oldv + (v - oldv) != v inside the clip range: the clipped
-      // branch then still carries the gradient 2 (v_clip - R)
-      const float kv = sc * cfg.value_coef * 0.5f * 2.0f;
-      float dv;
-      if (vl1 >= vl2) dv = kv * (v - R_);
-      else dv = (dvo >= -c && dvo <= c) ? kv * (vclip - R_) : 0.0f;
+      const float sc = cfg.loss_scale;
+      float pg, dlogp, vl, dv;
+      ac_loss_terms(true, adv, ratio, logp, v, oldv, R_, cfg.clip_norm, sc, cfg.value_coef, pg,
+                    dlogp, vl, dv);
       const float ec = sc * cfg.entropy_coef;
 #pragma unroll
       for (int a = 0; a < A; ++a)
