@@ -45,6 +45,10 @@
 #include "xa_adam.hpp"
 #include "xa_common.hpp"
 
+// (never called: a call that survives optimisation is a compile error, see the step loop)
+__device__ void xa_forms_not_unrolled()
+    __attribute__((error("ppo_update_kernel: the step loop's forms were not unrolled")));
+
 namespace {
 
 using namespace xa_ac;
@@ -413,24 +417,39 @@ __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a -
 
 __host__ __device__ inline int padded(int P) { return (P + 3) & ~3; }
 
+// byte offsets of the workspace arrays from its start (constants where G, P and K are)
+struct WsOff {
+  size_t ctl, persist, rows_g, g_g, adv, cen_g, xpart_g, total;
+};
+__host__ __device__ constexpr WsOff ws_off(int G, int P, int K) {
+  WsOff o{};
+  size_t off = 0;
+  const size_t PP = (size_t)((P + 3) & ~3);
+  const size_t bytes[7] = {(size_t)kCtlBytes, 256, (size_t)G * PP * 8, PP * 8 + (size_t)G * 64,
+                           (size_t)K * G * 2 * sizeof(double), (size_t)G * 16,
+                           (size_t)kXcds * PP * 16};
+  size_t at[7] = {};
+  for (int i = 0; i < 7; ++i) {
+    at[i] = off;
+    off = (off + bytes[i] + 255) / 256 * 256;
+  }
+  o.ctl = at[0], o.persist = at[1], o.rows_g = at[2], o.g_g = at[3], o.adv = at[4];
+  o.cen_g = at[5], o.xpart_g = at[6], o.total = off;
+  return o;
+}
+
 __host__ __device__ inline Ws carve(void* base, int G, int P, int K) {
   Ws w;
   char* c = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = c + off;
-    off = align_up(off + bytes, 256);
-    return q;
-  };
-  const size_t PP = padded(P);
-  w.ctl = (unsigned*)take(kCtlBytes);
-  w.persist = (unsigned*)take(256);
-  w.rows_g = take((size_t)G * PP * 8);
-  w.g_g = take(PP * 8 + (size_t)G * 64);
-  w.adv = (double*)take((size_t)K * G * 2 * sizeof(double));
-  w.cen_g = take((size_t)G * 16);
-  w.xpart_g = take((size_t)kXcds * PP * 16);
-  w.total = off;
+  const WsOff o = ws_off(G, P, K);
+  w.ctl = (unsigned*)(c + o.ctl);
+  w.persist = (unsigned*)(c + o.persist);
+  w.rows_g = c + o.rows_g;
+  w.g_g = c + o.g_g;
+  w.adv = (double*)(c + o.adv);
+  w.cen_g = c + o.cen_g;
+  w.xpart_g = c + o.xpart_g;
+  w.total = o.total;
   return w;
 }
 
@@ -673,9 +692,22 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   // ---- census: which XCD this block runs on (a granule, read after the phase-0 hop) ----
   // 16-sample tiles run only on small grids (<= 32 blocks): one level, known at compile time
   const bool two_level = BF == 2 || BF == 4 || (BF == 0 && !loc && TS == S && G >= kTwoLevelMinG);
-  const __amdgpu_buffer_rsrc_t cen_r = rsrc(ws.cen_g, (uint32_t)(G * 16));
+  // BF 1 / 3 (the one-level column-form kernels): ONE descriptor over the whole workspace and
+  // the arrays at byte offsets from its start (constants in the fixed-shape kernel): four
+  // SGPRs live through the step loop, not four per array. ws_off() is the layout carve() hands
+  // the host (carve is built from it; G is the launch's n_blocks, K its step count), so the
+  // offsets are the arrays' own. The hardware bound is the workspace's, no longer each
+  // array's: an offset past its array would land in the next one, so every offset below stays
+  // what it was under the per-array descriptors, and the 0 placeholders of unused poll
+  // slots (never loaded: masked by the slot count) now name the control words.
+  constexpr bool kOneRsrc = BF == 1 || BF == 3;
+  const WsOff wo = ws_off(G, P, K);
+  const __amdgpu_buffer_rsrc_t ws_r = rsrc(ws.ctl, (uint32_t)wo.total);
+  const uint32_t cen_o = kOneRsrc ? (uint32_t)wo.cen_g : 0u, adv_o = kOneRsrc ? (uint32_t)wo.adv : 0u;
+  const uint32_t rows_o = kOneRsrc ? (uint32_t)wo.rows_g : 0u, g_o = kOneRsrc ? (uint32_t)wo.g_g : 0u;
+  const __amdgpu_buffer_rsrc_t cen_r = kOneRsrc ? ws_r : rsrc(ws.cen_g, (uint32_t)(G * 16));
   if ((two_level || loc) && tid == 0)
-    st_gran2(cen_r, (uint32_t)(16 * b), __uint_as_float((unsigned)xcc),
+    st_gran2(cen_r, cen_o + (uint32_t)(16 * b), __uint_as_float((unsigned)xcc),
              __uint_as_float((unsigned)xcc), epoch, true);
 
   // ---- phase 0: advantage sums of this block's samples of every minibatch; their
@@ -692,7 +724,8 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   float* const advs = reinterpret_cast<float*>(U.red);
   // the blocks' per-minibatch advantage sums: tagged f64 pairs {s1, s2} (tag: the launch
   // epoch's parity), polled by every block -- the data is its own flag, no counter hop
-  const __amdgpu_buffer_rsrc_t adv_r = rsrc(ws.adv, (uint32_t)((size_t)K * G * 16));
+  const __amdgpu_buffer_rsrc_t adv_r =
+      kOneRsrc ? ws_r : rsrc(ws.adv, (uint32_t)((size_t)K * G * 16));
   const int per_k = TPB * TS;
   if (pre) {
     for (int i = tid; i < K * per_k; i += 256) {
@@ -753,7 +786,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
         s1 = s1 + xa_dpp_f64<0x142, 0xA>(s1);
         s2 = s2 + xa_dpp_f64<0x142, 0xA>(s2);
       }
-      if (k < K && j == RL - 1) st_d2_tagged(adv_r, (uint32_t)((k * G + b) * 16), s1, s2, epoch);
+      if (k < K && j == RL - 1) st_d2_tagged(adv_r, adv_o + (uint32_t)((k * G + b) * 16), s1, s2, epoch);
     }
   }
 #ifndef XA_ABL_P0
@@ -770,7 +803,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       }
       s1 = xa_wave_sum_f64(s1);
       s2 = xa_wave_sum_f64(s2);
-      if (lane == 0) st_d2_tagged(adv_r, (uint32_t)((k * G + b) * 16), s1, s2, epoch);
+      if (lane == 0) st_d2_tagged(adv_r, adv_o + (uint32_t)((k * G + b) * 16), s1, s2, epoch);
       continue;
     }
     const int e = k / n_mb, m = k - e * n_mb;
@@ -807,7 +840,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     }
     s1 = xa_wave_sum_f64(s1);
     s2 = xa_wave_sum_f64(s2);
-    if (lane == 0) st_d2_tagged(adv_r, (uint32_t)((k * G + b) * 16), s1, s2, epoch);
+    if (lane == 0) st_d2_tagged(adv_r, adv_o + (uint32_t)((k * G + b) * 16), s1, s2, epoch);
   }
   XA_TRACE_PT(b, kTraceSteps - 1, 1);  // advantage sums stored
   if (p.stats_words > 0) {
@@ -847,7 +880,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     int xt = -1;
     bool bad = false;
     if (tid < G) {
-      const uint32_t off[1] = {(uint32_t)(16 * tid)};
+      const uint32_t off[1] = {cen_o + (uint32_t)(16 * tid)};
       f32x4v v[1];
       bad = !poll_gran<1>(cen_r, off, 1, epoch, v, ws.ctl, epoch, p.status);
       xt = (int)__float_as_uint(v[0][0]);
@@ -878,7 +911,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   // XCD-local mode: thread t < G (wave 0: G < 64) reads candidate t's census granule; the
   // first load is issued here and returns under the advantage poll below
   f32x4v cen_v = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (loc && tid < G) cen_v = __builtin_amdgcn_raw_buffer_load_b128(cen_r, (uint32_t)(16 * tid), 0, kAuxSc1);
+  if (loc && tid < G) cen_v = __builtin_amdgcn_raw_buffer_load_b128(cen_r, cen_o + (uint32_t)(16 * tid), 0, kAuxSc1);
   {
     // the blocks' per-minibatch advantage sums: wave w sums minibatches w, w + 4, ...; it
     // issues the 16-B {s1, s2} sc1 loads of up to kAB (minibatch, block) pairs at once (one
@@ -895,7 +928,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
 #pragma unroll
       for (int u = 0; u < kAB; ++u) {
         const int j = j0 + u, kk = j / LPK, gi = lane + 64 * (j - kk * LPK);
-        off[u] = (uint32_t)(((w + 4 * kk) * G + gi) * 16);
+        off[u] = adv_o + (uint32_t)(((w + 4 * kk) * G + gi) * 16);
         if (j < nj && gi < G) valid |= 1u << u;
         x[u] = make_double2(0.0, 0.0);
       }
@@ -926,7 +959,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     bool other = false;
     if (tid < G) {
       if (!gran_ok(cen_v, epoch)) {
-        const uint32_t off[1] = {(uint32_t)(16 * tid)};
+        const uint32_t off[1] = {cen_o + (uint32_t)(16 * tid)};
         f32x4v v[1];
         dp_bad = !poll_gran<1>(cen_r, off, 1, epoch, v, ws.ctl, epoch, p.status) || dp_bad;
         cen_v = v[0];
@@ -1037,8 +1070,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   // phase B: block b reduces pair columns [c0, c0 + nc) of the gradient
   const int CB = (NP2 + G - 1) / G;
   const int c0 = min(NP2, b * CB), nc = min(NP2, c0 + CB) - c0;
-  const __amdgpu_buffer_rsrc_t rows_r = rsrc(ws.rows_g, (uint32_t)((size_t)G * PP * 8));
-  const __amdgpu_buffer_rsrc_t g_r = rsrc(ws.g_g, (uint32_t)(PP * 8 + G * 64));
+  const __amdgpu_buffer_rsrc_t rows_r =
+      kOneRsrc ? ws_r : rsrc(ws.rows_g, (uint32_t)((size_t)G * PP * 8));
+  const __amdgpu_buffer_rsrc_t g_r = kOneRsrc ? ws_r : rsrc(ws.g_g, (uint32_t)(PP * 8 + G * 64));
   const __amdgpu_buffer_rsrc_t xp_r = rsrc(ws.xpart_g, (uint32_t)(kXcds * PP * 16));
   float* srow = U.row;
   for (int i = P + tid; i < PP; i += 256) srow[i] = 0.0f;  // the pad stays zero
@@ -1083,502 +1117,530 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   };
   (void)k_tr;
   (void)stampf;
-  for (int k = 0; k < K; ++k) {
-    const int m = k % n_mb;
-    const int cnt = min(MB, B - m * MB);
-    const int n_tiles = (cnt + TS - 1) / TS;
-    const unsigned tag = tag_of(k);
-    // the LDS weights of the previous step's Adam: with the layer-1 weights in registers
-    // (kRegH1) the tile's first barrier orders them (H1 needs none of them), otherwise here
-    if constexpr (!kRegH1<OBS, A>) __syncthreads();
-    cfg.adv_mean = U.stat[k][0];
-    cfg.adv_std = U.stat[k][1];
-    cfg.adv_rstd = U.stat[k][2];
-    cfg.loss_scale = U.stat[k][3];
-    acc.zero();
-    if constexpr (!kRegH1<OBS, A>) load_w2_rows(L, w2r);
-    if (p.theta_trace && b == 0) ps.store(p.theta_trace + (size_t)k * P, wv, rv);  // diagnostic
-    XA_STAMP(34);
-    XA_TRACE_PT(b, k, 0);
-    k_tr = k;
-    // the block's gradient row in exchange order: the W2 part straight from the MFMA
-    // accumulators as granule pairs (from the last tile, overlapping its dH1 phase), the
-    // other parameters through LDS below
-    const bool row_wt = kWt && !two_level;
-    auto w2_out = [&](const PtAcc<OBS, A>& a) {
+  // The optimizer-step loop, one form per launch. The single-GPU one-level column-form
+  // kernels (BF 1 / 3 without DP, the XCD-local candidates) hold three copies of it, picked once here, behind the census
+  // verdict: form 0 is the general one (the hand-off store mode the run-time value it is,
+  // the optional outputs theta_trace / grad_trace / loss_out / grad_out read from the
+  // arguments) and runs when an output is requested; forms 1 and 2 have the store mode
+  // (write-through / plain) and "no optional output" as constants, so their bodies hold one
+  // store form and no output code. Every other kernel holds form 0 alone: the two-level-only
+  // kernels measured fastest with the store mode a run-time value, and the data-parallel
+  // kernels' steps wait on the cross-GPU exchange (nobody measured the forms there, and the
+  // compiler would not unroll the loop below in the one without preloaded inputs).
+  // The copies are the iterations of a fully unrolled loop over `form`, a constant in each
+  // copy: a one-trip loop leaves the code of the kernels that hold form 0 alone exactly as it
+  // was, which a function template or a lambda around the body did not. If
+  // the compiler ever declined to unroll it, xa_forms_not_unrolled() fails the build.
+  constexpr int kForms = (BF == 1 || BF == 3) && !DP ? 3 : 1;
+  // (kernel arguments and a readfirstlane'd flag: a scalar, the dispatch branches are uniform)
+  const int form_sel =
+      kForms == 1 || p.theta_trace || p.grad_trace || p.loss_out || p.grad_out ? 0 : kWt ? 1 : 2;
+  // an optional output's pointer: read in the general form, null in the specialised ones
+#define XA_OUT(f) ((kForms == 1 || form == 0) ? p.f : nullptr)
+#pragma unroll kForms
+  for (int form = 0; form < kForms; ++form) {
+    if (kForms > 1 && !__builtin_constant_p(form)) xa_forms_not_unrolled();
+    if (form != form_sel) continue;
+    if (kForms > 1 && form != 0) kWt = form == 1;  // (the value it has: a constant in this copy)
+    for (int k = 0; k < K; ++k) {
+      const int m = k % n_mb;
+      const int cnt = min(MB, B - m * MB);
+      const int n_tiles = (cnt + TS - 1) / TS;
+      const unsigned tag = tag_of(k);
+      // the LDS weights of the previous step's Adam: with the layer-1 weights in registers
+      // (kRegH1) the tile's first barrier orders them (H1 needs none of them), otherwise here
+      if constexpr (!kRegH1<OBS, A>) __syncthreads();
+      cfg.adv_mean = U.stat[k][0];
+      cfg.adv_std = U.stat[k][1];
+      cfg.adv_rstd = U.stat[k][2];
+      cfg.loss_scale = U.stat[k][3];
+      acc.zero();
+      if constexpr (!kRegH1<OBS, A>) load_w2_rows(L, w2r);
+      if (XA_OUT(theta_trace) && b == 0) ps.store(XA_OUT(theta_trace) + (size_t)k * P, wv, rv);  // diagnostic
+      XA_STAMP(34);
+      XA_TRACE_PT(b, k, 0);
+      k_tr = k;
+      // the block's gradient row in exchange order: the W2 part straight from the MFMA
+      // accumulators as granule pairs (from the last tile, overlapping its dH1 phase), the
+      // other parameters through LDS below
+      const bool row_wt = kWt && !two_level;
+      auto w2_out = [&](const PtAcc<OBS, A>& a) {
 #ifndef XA_ABL_ROW
-      pt_write_row_w2<OBS, A>(a, [&](int pr, float v0, float v1) {
-        st_row(rows_r, (uint32_t)((size_t)b * NP2 + pr) * kRowPB, v0, v1, tag, row_wt);
-      });
+        pt_write_row_w2<OBS, A>(a, [&](int pr, float v0, float v1) {
+          st_row(rows_r, rows_o + (uint32_t)((size_t)b * NP2 + pr) * kRowPB, v0, v1, tag, row_wt);
+        });
 #endif
-    };
-    // ---- A: forward + loss + backward of this block's tiles ----
-    for (int tile = b; tile < n_tiles; tile += G) {
-      const bool last = tile + G >= n_tiles;
-      if (pre) {
-        // inputs straight from the phase-0 records (read-only: no staging, no barrier)
-        XA_STAMP(35);
-        const float* in = &U.pre[((size_t)k * TPB * TS + ((tile - b) / G) * TS) * (OBS + 4)];
+      };
+      // ---- A: forward + loss + backward of this block's tiles ----
+      for (int tile = b; tile < n_tiles; tile += G) {
+        const bool last = tile + G >= n_tiles;
+        if (pre) {
+          // inputs straight from the phase-0 records (read-only: no staging, no barrier)
+          XA_STAMP(35);
+          const float* in = &U.pre[((size_t)k * TPB * TS + ((tile - b) / G) * TS) * (OBS + 4)];
 #ifndef XA_ABL_TILE  // diagnostic ablation builds (tools/ablate_update.py) only
-        pt_tile<OBS, A, TS>(L, acc, cfg, in, wv, w2r, rv[0], rv[1], stampf, last, w2_out);
+          pt_tile<OBS, A, TS>(L, acc, cfg, in, wv, w2r, rv[0], rv[1], stampf, last, w2_out);
 #else
-        if (last) w2_out(acc);
+          if (last) w2_out(acc);
 #endif
+          XA_STAMP(36);
+          XA_TRACE_PT(b, k, 14);
+          continue;
+        }
+        __syncthreads();  // the previous tile's reads of the staged records are done
+        if (tid < TS) {
+          float* rec = &U.stage[tid * (OBS + 4)];
+#pragma unroll
+          for (int kk = 0; kk < OBS; ++kk) rec[kk] = nx[kk];
+          rec[OBS] = n_valid ? n_act : -1.0f;
+          rec[OBS + 1] = n_ret;
+          rec[OBS + 2] = n_oldv;
+          rec[OBS + 3] = n_oldlp;
+        }
+        if (tile + G < n_tiles) fetch_tile(k, tile + G);
+        __syncthreads();
+        XA_STAMP(35);
+        pt_tile<OBS, A, TS>(L, acc, cfg, U.stage, wv, w2r, rv[0], rv[1], stampf, last, w2_out);
         XA_STAMP(36);
-        XA_TRACE_PT(b, k, 14);
-        continue;
       }
-      __syncthreads();  // the previous tile's reads of the staged records are done
-      if (tid < TS) {
-        float* rec = &U.stage[tid * (OBS + 4)];
-#pragma unroll
-        for (int kk = 0; kk < OBS; ++kk) rec[kk] = nx[kk];
-        rec[OBS] = n_valid ? n_act : -1.0f;
-        rec[OBS + 1] = n_ret;
-        rec[OBS + 2] = n_oldv;
-        rec[OBS + 3] = n_oldlp;
-      }
-      if (tile + G < n_tiles) fetch_tile(k, tile + G);
-      __syncthreads();
-      XA_STAMP(35);
-      pt_tile<OBS, A, TS>(L, acc, cfg, U.stage, wv, w2r, rv[0], rv[1], stampf, last, w2_out);
-      XA_STAMP(36);
-    }
-    if (b >= n_tiles) w2_out(acc);  // no tile of this minibatch: a zero row
-    // the rest of the row: 32-sample tiles store it straight from the lanes that hold its
-    // values, one tagged word each, plus the pad words behind P (no LDS staging, no barrier:
-    // C2 step 14.9 -> 14.4 us); 16-sample tiles stage it in LDS and store it coalesced
-    // behind a barrier (the scattered word stores made their step slower: 7.5 -> 7.9 us,
-    // profiles/r06v_ppo_update_trace.txt)
-    constexpr bool kRowDirect = TS == S;
+      if (b >= n_tiles) w2_out(acc);  // no tile of this minibatch: a zero row
+      // the rest of the row: 32-sample tiles store it straight from the lanes that hold its
+      // values, one tagged word each, plus the pad words behind P (no LDS staging, no barrier:
+      // C2 step 14.9 -> 14.4 us); 16-sample tiles stage it in LDS and store it coalesced
+      // behind a barrier (the scattered word stores made their step slower: 7.5 -> 7.9 us,
+      // profiles/r06v_ppo_update_trace.txt)
+      constexpr bool kRowDirect = TS == S;
 #ifndef XA_ABL_ROW
-    if constexpr (kRowDirect) {
-      pt_write_row_rest<OBS, A>(acc, [&](int x, float v) {
-        st_row1(rows_r, (uint32_t)(((size_t)b * NP2 * 2 + x) * 4), v, tag, row_wt);
-      }, p.loss_out != nullptr);
-      if (tid < PP - P)
-        st_row1(rows_r, (uint32_t)(((size_t)b * NP2 * 2 + P + tid) * 4), 0.0f, tag, row_wt);
-    } else {
-      pt_write_row_rest<OBS, A>(acc, [&](int x, float v) { srow[x] = v; }, p.loss_out != nullptr);
-    }
-#endif
-    XA_STAMP(44);
-    XA_TRACE_PT(b, k, 1);
-    if (p.loss_out && tid == 0) {
-      float* lo = p.loss_out + ((size_t)k * G + b) * 4;
-      lo[0] = acc.l_pg;
-      lo[1] = acc.l_v;
-      lo[2] = acc.l_ent;
-      lo[3] = acc.l_cnt;
-    }
-    if constexpr (!kRowDirect) {
-      __syncthreads();
-      for (int c = H * H / 2 + tid; c < NP2; c += 256)
-        st_row(rows_r, (uint32_t)((size_t)b * NP2 + c) * kRowPB, srow[2 * c], srow[2 * c + 1], tag,
-               row_wt);
-    } else if constexpr (BF == 0) {
-      // (the generic kernels' flat phase-B gather stages rows in the 32-sample tile's
-      // activation buffers, which the slowest wave's dH1 phase may still read)
-      __syncthreads();
-    }
-    XA_STAMP(45);
-    XA_TRACE_PT(b, k, 2);
-    fetch_tile(k + 1, b);  // the next step's first tile, while the other blocks finish
-    XA_STAMP(37);
-    if (two_level) {
-      // ---- level 1, inside the XCD: its members' rows (in this XCD's L2) -> this XCD's
-      // f64 partial of pair columns [xc0, xc0 + xnc), published write-through ----
-      const int ng = U.xn[xcc];
-      const int CBx = (NP2 + ng - 1) / ng;
-      const int xc0 = min(NP2, U.xrank * CBx), xnc = min(NP2, xc0 + CBx) - xc0;
-      const bool flat = false && ng * xnc <= 256 * kBF;  // measured slower at 32 rows (C2)
-      if (flat && xnc > 0) {
-        const bool bad = gather_rows(rows_r, ng, xnc, [&](int j) {
-          return (uint32_t)((size_t)U.xmem[j] * NP2 + xc0) * kRowPB;
-        }, tag);
-        if (__syncthreads_or(bad)) return;
-        for (int c = tid; c < xnc; c += 256) {
-          double t0 = 0.0, t1 = 0.0;
-          for (int j = 0; j < ng; ++j) {
-            t0 += (double)scr[2 * (j * xnc + c)];
-            t1 += (double)scr[2 * (j * xnc + c) + 1];
-          }
-          st_d2_tagged(xp_r, (uint32_t)(((size_t)xcc * NP2 + xc0 + c) * 16), t0, t1, tag);
-        }
-        __syncthreads();
-      }
-      const int ncol = max(1, min(xnc, 256)), RG = 256 / ncol;
-      const int rg = tid / ncol, cq = tid - rg * ncol;
-      for (int cb = 0; !flat && cb < xnc; cb += ncol) {
-        bool bad = false;
-        if (rg < RG && cb + cq < xnc) {
-          const int c = xc0 + cb + cq;
-          double a0 = 0.0, a1 = 0.0;
-          constexpr int kB = kBF;  // 32 XCD members over 3 row groups: one poll round
-          for (int j0 = rg; j0 < ng && !bad; j0 += RG * kB) {
-            uint32_t off[kB];
-            RowG x[kB];
-            int n = 0;
-#pragma unroll
-            for (int u = 0; u < kB; ++u) {
-              const int j = j0 + u * RG;
-              off[u] = j < ng ? (uint32_t)((size_t)U.xmem[j] * NP2 + c) * kRowPB : 0u;
-              n += j < ng;
-            }
-            bad = !poll_row<kB>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
-#pragma unroll
-            for (int u = 0; u < kB; ++u)
-              if (u < n) {
-                a0 += (double)row_v0(x[u]);
-                a1 += (double)row_v1(x[u]);
-              }
-          }
-          U.red[(rg * ncol + cq) * 2] = a0;
-          U.red[(rg * ncol + cq) * 2 + 1] = a1;
-        }
-        if (__syncthreads_or(bad)) return;
-        if (tid < ncol && cb + tid < xnc) {
-          double t0 = 0.0, t1 = 0.0;
-          for (int r = 0; r < RG; ++r) {
-            t0 += U.red[(r * ncol + tid) * 2];
-            t1 += U.red[(r * ncol + tid) * 2 + 1];
-          }
-          st_d2_tagged(xp_r, (uint32_t)(((size_t)xcc * NP2 + xc0 + cb + tid) * 16), t0, t1, tag);
-        }
-        __syncthreads();
-      }
-    }
-    XA_STAMP(38);
-
-    // ---- B: pair columns [c0, c0 + nc): the fixed-order sum over the G rows, or
-    // (two-level) over the XCD partials in XCD order -> g (granules) + f64 sum of squares ----
-    double sq = 0.0;
-    // pair column c of this block's slice: publish the final value (g granules, the last
-    // step's raw gradient, the sum of squares), or -- data parallel -- stage the rank's local
-    // value in srow for the cross-rank exchange below
-    auto publish = [&](int c, float g0, float g1) {
-      const int cc = c0 + c;
-      st_row(g_r, (uint32_t)cc * kRowPB, g0, g1, tag, kWt);
-      // canonical order for the caller (exchange index -> flat parameter index)
-      if (p.grad_out && k == K - 1) {
-        if (2 * cc < P) p.grad_out[canon_of_exchange<OBS, A>(2 * cc)] = g0;
-        if (2 * cc + 1 < P) p.grad_out[canon_of_exchange<OBS, A>(2 * cc + 1)] = g1;
-      }
-      if (p.grad_trace) {  // diagnostic: every step's reduced gradient
-        float* gt = p.grad_trace + (size_t)k * P;
-        if (2 * cc < P) gt[canon_of_exchange<OBS, A>(2 * cc)] = g0;
-        if (2 * cc + 1 < P) gt[canon_of_exchange<OBS, A>(2 * cc + 1)] = g1;
-      }
-      sq += (double)g0 * (double)g0 + (double)g1 * (double)g1;
-    };
-    auto emit = [&](int c, float g0, float g1) {
-      if constexpr (DP) {
-        srow[2 * c] = g0;
-        srow[2 * c + 1] = g1;
+      if constexpr (kRowDirect) {
+        pt_write_row_rest<OBS, A>(acc, [&](int x, float v) {
+          st_row1(rows_r, rows_o + (uint32_t)(((size_t)b * NP2 * 2 + x) * 4), v, tag, row_wt);
+        }, XA_OUT(loss_out) != nullptr);
+        if (tid < PP - P)
+          st_row1(rows_r, rows_o + (uint32_t)(((size_t)b * NP2 * 2 + P + tid) * 4), 0.0f, tag,
+                  row_wt);
       } else {
-        publish(c, g0, g1);
+        pt_write_row_rest<OBS, A>(acc, [&](int x, float v) { srow[x] = v; }, XA_OUT(loss_out) != nullptr);
       }
-    };
-    // few columns, few rows per part: thread (part, c) polls its own column's rows part,
-    // part + parts, ... (<= kBF granules, one round trip) and sums them in registers in
-    // that order -- the flat path's arithmetic without its LDS staging pass
-    const int parts_b = nc <= 128 ? min(4, 256 / max(nc, 1)) : 1;
-    const bool col_b = !two_level && nc > 0 && parts_b > 1 && (G + parts_b - 1) / parts_b <= kBF;
-    if (col_b) {
-      double t0 = 0.0, t1 = 0.0;
-      bool bad = false;
-      if (tid < parts_b * nc) {
-        const int part = tid / nc, c = tid - part * nc;
-        uint32_t off[kBF];
-        RowG x[kBF];
-        int n = 0;
-#pragma unroll
-        for (int u = 0; u < kBF; ++u) {
-          const int r = part + parts_b * u;
-          off[u] = r < G ? (uint32_t)((size_t)r * NP2 + c0 + c) * kRowPB : 0u;
-          n += r < G;
-        }
-        bad = !poll_row<kBF>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
-#pragma unroll
-        for (int u = 0; u < kBF; ++u)
-          if (u < n) {
-            t0 += (double)row_v0(x[u]);
-            t1 += (double)row_v1(x[u]);
-          }
-        U.red[(part * nc + c) * 2] = t0;
-        U.red[(part * nc + c) * 2 + 1] = t1;
-      }
-      if (__syncthreads_or(bad)) return;
-      for (int c = tid; c < nc; c += 256) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int part = 0; part < parts_b; ++part) {
-          s0 += U.red[(part * nc + c) * 2];
-          s1 += U.red[(part * nc + c) * 2 + 1];
-        }
-        const float g0 = (float)s0, g1 = (float)s1;
-        emit(c, g0, g1);
-      }
-    }
-    // (BF = 1: the host guarantees col_b wherever nc > 0; BF = 2: two_level everywhere)
-    constexpr bool flat_ok = BF == 0, gen_ok = BF != 1 && BF != 3;
-    const bool flat_b = flat_ok && !col_b && !two_level && G * nc <= 256 * kBF;
-    if (nc > 0 && flat_b) {
-      const bool bad = gather_rows(rows_r, G, nc, [&](int r) {
-        return (uint32_t)((size_t)r * NP2 + c0) * kRowPB;
-      }, tag);
-      if (__syncthreads_or(bad)) return;
-      // few columns: `parts` threads per column sum interleaved rows, combined in part
-      // order (a shorter dependent f64 chain; fixed order)
-      const int parts = nc <= 128 ? min(4, 256 / nc) : 1;
-#ifdef XA_ABL_BSUM
-      if (false) {
-#else
-      if (parts > 1) {
 #endif
-        if (tid < parts * nc) {
-          const int part = tid / nc, c = tid - part * nc;
-          double t0 = 0.0, t1 = 0.0;
-          for (int r = part; r < G; r += parts) {
-            t0 += (double)scr[2 * (r * nc + c)];
-            t1 += (double)scr[2 * (r * nc + c) + 1];
-          }
-          U.red[(part * nc + c) * 2] = t0;
-          U.red[(part * nc + c) * 2 + 1] = t1;
-        }
+      XA_STAMP(44);
+      XA_TRACE_PT(b, k, 1);
+      if (XA_OUT(loss_out) && tid == 0) {
+        float* lo = XA_OUT(loss_out) + ((size_t)k * G + b) * 4;
+        lo[0] = acc.l_pg;
+        lo[1] = acc.l_v;
+        lo[2] = acc.l_ent;
+        lo[3] = acc.l_cnt;
+      }
+      if constexpr (!kRowDirect) {
+        __syncthreads();
+        for (int c = H * H / 2 + tid; c < NP2; c += 256)
+          st_row(rows_r, rows_o + (uint32_t)((size_t)b * NP2 + c) * kRowPB, srow[2 * c],
+                 srow[2 * c + 1], tag, row_wt);
+      } else if constexpr (BF == 0) {
+        // (the generic kernels' flat phase-B gather stages rows in the 32-sample tile's
+        // activation buffers, which the slowest wave's dH1 phase may still read)
         __syncthreads();
       }
-      for (int c = tid; c < nc; c += 256) {
-        double t0 = 0.0, t1 = 0.0;
-#ifdef XA_ABL_BSUM
-        if (true) {
-          t0 = scr[2 * c]; t1 = scr[2 * c + 1];
-        } else
-#endif
-        if (parts > 1) {
-          for (int part = 0; part < parts; ++part) {
-            t0 += U.red[(part * nc + c) * 2];
-            t1 += U.red[(part * nc + c) * 2 + 1];
+      XA_STAMP(45);
+      XA_TRACE_PT(b, k, 2);
+      fetch_tile(k + 1, b);  // the next step's first tile, while the other blocks finish
+      XA_STAMP(37);
+      if (two_level) {
+        // ---- level 1, inside the XCD: its members' rows (in this XCD's L2) -> this XCD's
+        // f64 partial of pair columns [xc0, xc0 + xnc), published write-through ----
+        const int ng = U.xn[xcc];
+        const int CBx = (NP2 + ng - 1) / ng;
+        const int xc0 = min(NP2, U.xrank * CBx), xnc = min(NP2, xc0 + CBx) - xc0;
+        const bool flat = false && ng * xnc <= 256 * kBF;  // measured slower at 32 rows (C2)
+        if (flat && xnc > 0) {
+          const bool bad = gather_rows(rows_r, ng, xnc, [&](int j) {
+            return rows_o + (uint32_t)((size_t)U.xmem[j] * NP2 + xc0) * kRowPB;
+          }, tag);
+          if (__syncthreads_or(bad)) return;
+          for (int c = tid; c < xnc; c += 256) {
+            double t0 = 0.0, t1 = 0.0;
+            for (int j = 0; j < ng; ++j) {
+              t0 += (double)scr[2 * (j * xnc + c)];
+              t1 += (double)scr[2 * (j * xnc + c) + 1];
+            }
+            st_d2_tagged(xp_r, (uint32_t)(((size_t)xcc * NP2 + xc0 + c) * 16), t0, t1, tag);
           }
-        } else {
-          for (int r = 0; r < G; ++r) {
-            t0 += (double)scr[2 * (r * nc + c)];
-            t1 += (double)scr[2 * (r * nc + c) + 1];
-          }
+          __syncthreads();
         }
-        const float g0 = (float)t0, g1 = (float)t1;
-        emit(c, g0, g1);
-      }
-    }
-    if (gen_ok && nc > 0 && !flat_b && !col_b) {
-      const int SRC = two_level ? kXcds : G;  // sources summed per column
-      const int ncol = min(nc, 256), RG = min(SRC, 256 / ncol);
-      const int rg = tid / ncol, cq = tid - rg * ncol;
-      for (int cb = 0; cb < nc; cb += ncol) {
-        bool bad = false;
-        if (rg < RG && cb + cq < nc) {
-          const int c = c0 + cb + cq;
-          double a0 = 0.0, a1 = 0.0;
-          constexpr int kB = 8;
-          for (int j0 = rg; j0 < SRC && !bad; j0 += RG * kB) {
-            uint32_t off[kB];
-            int n = 0;
-            if (two_level) {
-              // one tagged f64 pair per pair column and XCD
-              double2 x[kB];
-#pragma unroll
-              for (int u = 0; u < kB; ++u) off[u] = 0u;
-              for (int u = 0; u < kB; ++u) {
-                const int xx = j0 + u * RG;
-                if (xx < kXcds && U.xn[xx] > 0) off[n++] = (uint32_t)(((size_t)xx * NP2 + c) * 16);
-              }
-              bad = !poll_d2<kB>(xp_r, off, (1u << n) - 1u, tag, x, ws.ctl, epoch, p.status);
-              for (int u = 0; u < n; ++u) {
-                a0 += x[u].x;
-                a1 += x[u].y;
-              }
-            } else {
-              RowG xr[kB];
+        const int ncol = max(1, min(xnc, 256)), RG = 256 / ncol;
+        const int rg = tid / ncol, cq = tid - rg * ncol;
+        for (int cb = 0; !flat && cb < xnc; cb += ncol) {
+          bool bad = false;
+          if (rg < RG && cb + cq < xnc) {
+            const int c = xc0 + cb + cq;
+            double a0 = 0.0, a1 = 0.0;
+            constexpr int kB = kBF;  // 32 XCD members over 3 row groups: one poll round
+            for (int j0 = rg; j0 < ng && !bad; j0 += RG * kB) {
+              uint32_t off[kB];
+              RowG x[kB];
+              int n = 0;
 #pragma unroll
               for (int u = 0; u < kB; ++u) {
-                const int r = j0 + u * RG;
-                off[u] = r < G ? (uint32_t)((size_t)r * NP2 + c) * kRowPB : 0u;
-                n += r < G;
+                const int j = j0 + u * RG;
+                off[u] = j < ng ? rows_o + (uint32_t)((size_t)U.xmem[j] * NP2 + c) * kRowPB : 0u;
+                n += j < ng;
               }
-              bad = !poll_row<kB>(rows_r, off, n, tag, xr, ws.ctl, epoch, p.status);
+              bad = !poll_row<kB>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
 #pragma unroll
               for (int u = 0; u < kB; ++u)
                 if (u < n) {
-                  a0 += (double)row_v0(xr[u]);
-                  a1 += (double)row_v1(xr[u]);
+                  a0 += (double)row_v0(x[u]);
+                  a1 += (double)row_v1(x[u]);
                 }
             }
+            U.red[(rg * ncol + cq) * 2] = a0;
+            U.red[(rg * ncol + cq) * 2 + 1] = a1;
           }
-          U.red[(rg * ncol + cq) * 2] = a0;
-          U.red[(rg * ncol + cq) * 2 + 1] = a1;
+          if (__syncthreads_or(bad)) return;
+          if (tid < ncol && cb + tid < xnc) {
+            double t0 = 0.0, t1 = 0.0;
+            for (int r = 0; r < RG; ++r) {
+              t0 += U.red[(r * ncol + tid) * 2];
+              t1 += U.red[(r * ncol + tid) * 2 + 1];
+            }
+            st_d2_tagged(xp_r, (uint32_t)(((size_t)xcc * NP2 + xc0 + cb + tid) * 16), t0, t1, tag);
+          }
+          __syncthreads();
+        }
+      }
+      XA_STAMP(38);
+
+      // ---- B: pair columns [c0, c0 + nc): the fixed-order sum over the G rows, or
+      // (two-level) over the XCD partials in XCD order -> g (granules) + f64 sum of squares ----
+      double sq = 0.0;
+      // pair column c of this block's slice: publish the final value (g granules, the last
+      // step's raw gradient, the sum of squares), or -- data parallel -- stage the rank's local
+      // value in srow for the cross-rank exchange below
+      auto publish = [&](int c, float g0, float g1) {
+        const int cc = c0 + c;
+        st_row(g_r, g_o + (uint32_t)cc * kRowPB, g0, g1, tag, kWt);
+        // canonical order for the caller (exchange index -> flat parameter index)
+        if (XA_OUT(grad_out) && k == K - 1) {
+          if (2 * cc < P) XA_OUT(grad_out)[canon_of_exchange<OBS, A>(2 * cc)] = g0;
+          if (2 * cc + 1 < P) XA_OUT(grad_out)[canon_of_exchange<OBS, A>(2 * cc + 1)] = g1;
+        }
+        if (XA_OUT(grad_trace)) {  // diagnostic: every step's reduced gradient
+          float* gt = XA_OUT(grad_trace) + (size_t)k * P;
+          if (2 * cc < P) gt[canon_of_exchange<OBS, A>(2 * cc)] = g0;
+          if (2 * cc + 1 < P) gt[canon_of_exchange<OBS, A>(2 * cc + 1)] = g1;
+        }
+        sq += (double)g0 * (double)g0 + (double)g1 * (double)g1;
+      };
+      auto emit = [&](int c, float g0, float g1) {
+        if constexpr (DP) {
+          srow[2 * c] = g0;
+          srow[2 * c + 1] = g1;
+        } else {
+          publish(c, g0, g1);
+        }
+      };
+      // few columns, few rows per part: thread (part, c) polls its own column's rows part,
+      // part + parts, ... (<= kBF granules, one round trip) and sums them in registers in
+      // that order -- the flat path's arithmetic without its LDS staging pass
+      const int parts_b = nc <= 128 ? min(4, 256 / max(nc, 1)) : 1;
+      const bool col_b = !two_level && nc > 0 && parts_b > 1 && (G + parts_b - 1) / parts_b <= kBF;
+      if (col_b) {
+        double t0 = 0.0, t1 = 0.0;
+        bool bad = false;
+        if (tid < parts_b * nc) {
+          const int part = tid / nc, c = tid - part * nc;
+          uint32_t off[kBF];
+          RowG x[kBF];
+          int n = 0;
+#pragma unroll
+          for (int u = 0; u < kBF; ++u) {
+            const int r = part + parts_b * u;
+            off[u] = r < G ? rows_o + (uint32_t)((size_t)r * NP2 + c0 + c) * kRowPB : 0u;
+            n += r < G;
+          }
+          bad = !poll_row<kBF>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
+#pragma unroll
+          for (int u = 0; u < kBF; ++u)
+            if (u < n) {
+              t0 += (double)row_v0(x[u]);
+              t1 += (double)row_v1(x[u]);
+            }
+          U.red[(part * nc + c) * 2] = t0;
+          U.red[(part * nc + c) * 2 + 1] = t1;
         }
         if (__syncthreads_or(bad)) return;
-        if (tid < ncol && cb + tid < nc) {
+        for (int c = tid; c < nc; c += 256) {
+          double s0 = 0.0, s1 = 0.0;
+          for (int part = 0; part < parts_b; ++part) {
+            s0 += U.red[(part * nc + c) * 2];
+            s1 += U.red[(part * nc + c) * 2 + 1];
+          }
+          const float g0 = (float)s0, g1 = (float)s1;
+          emit(c, g0, g1);
+        }
+      }
+      // (BF = 1: the host guarantees col_b wherever nc > 0; BF = 2: two_level everywhere)
+      constexpr bool flat_ok = BF == 0, gen_ok = BF != 1 && BF != 3;
+      const bool flat_b = flat_ok && !col_b && !two_level && G * nc <= 256 * kBF;
+      if (nc > 0 && flat_b) {
+        const bool bad = gather_rows(rows_r, G, nc, [&](int r) {
+          return rows_o + (uint32_t)((size_t)r * NP2 + c0) * kRowPB;
+        }, tag);
+        if (__syncthreads_or(bad)) return;
+        // few columns: `parts` threads per column sum interleaved rows, combined in part
+        // order (a shorter dependent f64 chain; fixed order)
+        const int parts = nc <= 128 ? min(4, 256 / nc) : 1;
+#ifdef XA_ABL_BSUM
+        if (false) {
+#else
+        if (parts > 1) {
+#endif
+          if (tid < parts * nc) {
+            const int part = tid / nc, c = tid - part * nc;
+            double t0 = 0.0, t1 = 0.0;
+            for (int r = part; r < G; r += parts) {
+              t0 += (double)scr[2 * (r * nc + c)];
+              t1 += (double)scr[2 * (r * nc + c) + 1];
+            }
+            U.red[(part * nc + c) * 2] = t0;
+            U.red[(part * nc + c) * 2 + 1] = t1;
+          }
+          __syncthreads();
+        }
+        for (int c = tid; c < nc; c += 256) {
           double t0 = 0.0, t1 = 0.0;
-          for (int r = 0; r < RG; ++r) {
-            t0 += U.red[(r * ncol + tid) * 2];
-            t1 += U.red[(r * ncol + tid) * 2 + 1];
+#ifdef XA_ABL_BSUM
+          if (true) {
+            t0 = scr[2 * c]; t1 = scr[2 * c + 1];
+          } else
+#endif
+          if (parts > 1) {
+            for (int part = 0; part < parts; ++part) {
+              t0 += U.red[(part * nc + c) * 2];
+              t1 += U.red[(part * nc + c) * 2 + 1];
+            }
+          } else {
+            for (int r = 0; r < G; ++r) {
+              t0 += (double)scr[2 * (r * nc + c)];
+              t1 += (double)scr[2 * (r * nc + c) + 1];
+            }
           }
           const float g0 = (float)t0, g1 = (float)t1;
-          emit(cb + tid, g0, g1);
-        }
-        __syncthreads();
-      }
-    }
-    if constexpr (DP) {
-      // push this rank's slice to every rank (parity k & 1), then read every rank's slice
-      // from the own block and sum in rank order (f64) -> the union's gradient slice
-      __syncthreads();  // srow holds the local slice
-      const int par = k & 1;
-      for (int c = tid; c < nc; c += 256) {
-        const size_t o = dl.gsl + ((((size_t)par * G + b) * W + p.dp_rank) * CB0 + c) * 16;
-        const uint32_t w0 = __float_as_uint(srow[2 * c]), w1 = __float_as_uint(srow[2 * c + 1]);
-        for (int q = 0; q < W; ++q) {
-          dp_st(p.dp_blocks[q], o, w0, tag);
-          dp_st(p.dp_blocks[q], o + 8, w1, tag);
+          emit(c, g0, g1);
         }
       }
-      bool bad = false;
-      for (int c = tid; c < nc; c += 256) {
-        constexpr int kW2 = 2 * XA_PPO_DP_MAX;
-        size_t off[kW2];
-        uint32_t x[kW2];
+      if (gen_ok && nc > 0 && !flat_b && !col_b) {
+        const int SRC = two_level ? kXcds : G;  // sources summed per column
+        const int ncol = min(nc, 256), RG = min(SRC, 256 / ncol);
+        const int rg = tid / ncol, cq = tid - rg * ncol;
+        for (int cb = 0; cb < nc; cb += ncol) {
+          bool bad = false;
+          if (rg < RG && cb + cq < nc) {
+            const int c = c0 + cb + cq;
+            double a0 = 0.0, a1 = 0.0;
+            constexpr int kB = 8;
+            for (int j0 = rg; j0 < SRC && !bad; j0 += RG * kB) {
+              uint32_t off[kB];
+              int n = 0;
+              if (two_level) {
+                // one tagged f64 pair per pair column and XCD
+                double2 x[kB];
 #pragma unroll
-        for (int u = 0; u < kW2; ++u) {
-          const int r = u >> 1;
-          off[u] = r < W ? dl.gsl + ((((size_t)par * G + b) * W + r) * CB0 + c) * 16 + 8 * (u & 1)
-                         : 0;
+                for (int u = 0; u < kB; ++u) off[u] = 0u;
+                for (int u = 0; u < kB; ++u) {
+                  const int xx = j0 + u * RG;
+                  if (xx < kXcds && U.xn[xx] > 0) off[n++] = (uint32_t)(((size_t)xx * NP2 + c) * 16);
+                }
+                bad = !poll_d2<kB>(xp_r, off, (1u << n) - 1u, tag, x, ws.ctl, epoch, p.status);
+                for (int u = 0; u < n; ++u) {
+                  a0 += x[u].x;
+                  a1 += x[u].y;
+                }
+              } else {
+                RowG xr[kB];
+#pragma unroll
+                for (int u = 0; u < kB; ++u) {
+                  const int r = j0 + u * RG;
+                  off[u] = r < G ? rows_o + (uint32_t)((size_t)r * NP2 + c) * kRowPB : 0u;
+                  n += r < G;
+                }
+                bad = !poll_row<kB>(rows_r, off, n, tag, xr, ws.ctl, epoch, p.status);
+#pragma unroll
+                for (int u = 0; u < kB; ++u)
+                  if (u < n) {
+                    a0 += (double)row_v0(xr[u]);
+                    a1 += (double)row_v1(xr[u]);
+                  }
+              }
+            }
+            U.red[(rg * ncol + cq) * 2] = a0;
+            U.red[(rg * ncol + cq) * 2 + 1] = a1;
+          }
+          if (__syncthreads_or(bad)) return;
+          if (tid < ncol && cb + tid < nc) {
+            double t0 = 0.0, t1 = 0.0;
+            for (int r = 0; r < RG; ++r) {
+              t0 += U.red[(r * ncol + tid) * 2];
+              t1 += U.red[(r * ncol + tid) * 2 + 1];
+            }
+            const float g0 = (float)t0, g1 = (float)t1;
+            emit(cb + tid, g0, g1);
+          }
+          __syncthreads();
         }
-        bad = bad || !dp_poll<kW2>(p.dp_blocks[p.dp_rank], off, 2 * W, tag, x, ws.ctl, epoch,
-                                   p.status);
-        double s0 = 0.0, s1 = 0.0;
-        for (int r = 0; r < W; ++r) {
-          s0 += (double)__uint_as_float(x[2 * r]);
-          s1 += (double)__uint_as_float(x[2 * r + 1]);
-        }
-        publish(c, (float)s0, (float)s1);
       }
-      if (__syncthreads_or(bad)) return;
-    }
-    (void)sq;
-    XA_STAMP(40);
-    XA_TRACE_PT(b, k, 3);
+      if constexpr (DP) {
+        // push this rank's slice to every rank (parity k & 1), then read every rank's slice
+        // from the own block and sum in rank order (f64) -> the union's gradient slice
+        __syncthreads();  // srow holds the local slice
+        const int par = k & 1;
+        for (int c = tid; c < nc; c += 256) {
+          const size_t o = dl.gsl + ((((size_t)par * G + b) * W + p.dp_rank) * CB0 + c) * 16;
+          const uint32_t w0 = __float_as_uint(srow[2 * c]), w1 = __float_as_uint(srow[2 * c + 1]);
+          for (int q = 0; q < W; ++q) {
+            dp_st(p.dp_blocks[q], o, w0, tag);
+            dp_st(p.dp_blocks[q], o + 8, w1, tag);
+          }
+        }
+        bool bad = false;
+        for (int c = tid; c < nc; c += 256) {
+          constexpr int kW2 = 2 * XA_PPO_DP_MAX;
+          size_t off[kW2];
+          uint32_t x[kW2];
+#pragma unroll
+          for (int u = 0; u < kW2; ++u) {
+            const int r = u >> 1;
+            off[u] = r < W ? dl.gsl + ((((size_t)par * G + b) * W + r) * CB0 + c) * 16 + 8 * (u & 1)
+                           : 0;
+          }
+          bad = bad || !dp_poll<kW2>(p.dp_blocks[p.dp_rank], off, 2 * W, tag, x, ws.ctl, epoch,
+                                     p.status);
+          double s0 = 0.0, s1 = 0.0;
+          for (int r = 0; r < W; ++r) {
+            s0 += (double)__uint_as_float(x[2 * r]);
+            s1 += (double)__uint_as_float(x[2 * r + 1]);
+          }
+          publish(c, (float)s0, (float)s1);
+        }
+        if (__syncthreads_or(bad)) return;
+      }
+      (void)sq;
+      XA_STAMP(40);
+      XA_TRACE_PT(b, k, 3);
 
-    // ---- C: the g slice of this thread's parameters and the G norm partials (granules of
-    // one buffer, one poll), global norm (identical in every wave of every block), clip +
-    // Keras Adam ----
-    float gw[16], gr[RPT];
-    double tot = 0.0;
-    bool bad = false;
-    // the gradient-free half of the Adam moment updates, before the poll (its loads and
-    // multiplies leave the critical path): b1 m and b2 v of the thread's slots
-    float bm[4 * NQ4], bv[4 * NQ4];
-#pragma unroll
-    for (int q4 = 0; q4 < NQ4; ++q4) {
-      const float4 a = U.mv4[0][q4][tid], c = U.mv4[1][q4][tid];
-      const xa_f2 b1 = {p.adam.beta1, p.adam.beta1}, b2 = {p.adam.beta2, p.adam.beta2};
-      const xa_f2 m01 = xa_f2{a.x, a.y} * b1, m23 = xa_f2{a.z, a.w} * b1;
-      const xa_f2 v01 = xa_f2{c.x, c.y} * b2, v23 = xa_f2{c.z, c.w} * b2;
-      bm[4 * q4] = m01.x; bm[4 * q4 + 1] = m01.y; bm[4 * q4 + 2] = m23.x; bm[4 * q4 + 3] = m23.y;
-      bv[4 * q4] = v01.x; bv[4 * q4 + 1] = v01.y; bv[4 * q4 + 2] = v23.x; bv[4 * q4 + 3] = v23.y;
-    }
-    {
-      // the thread's g values: 8 W2 pairs (exchange order: pairs 256 h + tid, coalesced) and
-      // its rest pairs, as tagged pairs in one poll
-      constexpr int NG = 8 + RPT;
-      uint32_t off[NG];
-      RowG x[NG];
-#pragma unroll
-      for (int h = 0; h < 8; ++h) off[h] = (uint32_t)((256 * h + tid) * kRowPB);
-#pragma unroll
-      for (int q = 0; q < RPT; ++q)
-        off[8 + q] = (uint32_t)((ps.rx[q] >= 0 ? ps.rx[q] / 2 : 0) * kRowPB);
-      bad = !poll_row<NG>(g_r, off, NG, tag, x, ws.ctl, epoch, p.status);
-      XA_STAMP(46);
-#pragma unroll
-      for (int h = 0; h < 8; ++h) {
-        gw[2 * h] = row_v0(x[h]);
-        gw[2 * h + 1] = row_v1(x[h]);
-      }
-#pragma unroll
-      for (int q = 0; q < RPT; ++q)
-        gr[q] = ps.rx[q] >= 0 ? ((ps.rx[q] & 1) ? row_v1(x[8 + q]) : row_v0(x[8 + q])) : 0.0f;
-    }
-    {
-      // the block holds all of g (each parameter on exactly one thread): its own f64 sum of
-      // squares in a fixed thread / wave order, identical in every block
-      double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) {
-        s0 = fma((double)gw[q], (double)gw[q], s0);
-        s1 = fma((double)gw[q + 1], (double)gw[q + 1], s1);
-      }
-#pragma unroll
-      for (int q = 0; q < RPT; ++q) s0 = fma((double)gr[q], (double)gr[q], s0);
-      const double ws = xa_wave_sum_f64(s0 + s1);
-      if (lane == 0) U.wsum[w] = ws;
-    }
-    if (__syncthreads_or(bad)) return;
-    XA_STAMP(47);
-    XA_TRACE_PT(b, k, 4);
-#ifndef XA_ABL_CNORM
-    tot = (U.wsum[0] + U.wsum[1]) + (U.wsum[2] + U.wsum[3]);
-    // tf.clip_by_global_norm's scale clip * min(1 / norm, 1 / clip), on the hardware sqrt /
-    // reciprocal units (the update is checked against float64 with a tolerance)
-    const float gn = __builtin_amdgcn_sqrtf((float)tot);
-    const float sc = p.adam.clip_norm > 0.0f
-                         ? p.adam.clip_norm * fminf(frcp(gn), frcp(p.adam.clip_norm)) : 1.0f;
-#else
-    const float sc = (float)tot;
-#endif
-    const float alpha = U.alpha[k];
-#ifndef XA_ABL_ADAM
-    {
-      // m' = b1 m + (1 - b1) sc g, v' = b2 v + (1 - b2) sc^2 g^2 (Keras ApplyAdam on the
-      // clipped gradient sc g, regrouped: the update is checked against float64 with a
-      // tolerance), theta -= alpha m' / (sqrt(v') + eps)
-      const xa_f2 k1 = {sc * omb1, sc * omb1}, k2 = {(sc * sc) * omb2, (sc * sc) * omb2};
-      const xa_f2 al = {alpha, alpha}, ep = {p.adam.eps, p.adam.eps};
-      float th[4 * NQ4];
-#pragma unroll
-      for (int q = 0; q < 4 * NQ4; ++q) th[q] = q < 16 ? wv[q] : q < NS ? rv[q - 16] : 0.0f;
-#pragma unroll
-      for (int q = 0; q < NS; q += 2) {
-        const xa_f2 g = {q < 16 ? gw[q] : gr[q - 16], q + 1 < 16 ? gw[q + 1] : q + 1 < NS ? gr[q + 1 - 16] : 0.0f};
-        const xa_f2 mn = xa_fma2(g, k1, xa_f2{bm[q], bm[q + 1]});
-        const xa_f2 vn = xa_fma2(g * g, k2, xa_f2{bv[q], bv[q + 1]});
-        const xa_f2 step = mn * al;
-        const xa_f2 den = xa_f2{__builtin_amdgcn_sqrtf(vn.x), __builtin_amdgcn_sqrtf(vn.y)} + ep;
-        const xa_f2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-        const xa_f2 tn = xa_fma2(-step, r, xa_f2{th[q], th[q + 1]});
-        th[q] = tn.x;
-        th[q + 1] = tn.y;
-        bm[q] = mn.x;
-        bm[q + 1] = mn.y;
-        bv[q] = vn.x;
-        bv[q + 1] = vn.y;
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) wv[q] = th[q];
-#pragma unroll
-      for (int q = 0; q < RPT; ++q) rv[q] = th[16 + q];
+      // ---- C: the g slice of this thread's parameters and the G norm partials (granules of
+      // one buffer, one poll), global norm (identical in every wave of every block), clip +
+      // Keras Adam ----
+      float gw[16], gr[RPT];
+      double tot = 0.0;
+      bool bad = false;
+      // the gradient-free half of the Adam moment updates, before the poll (its loads and
+      // multiplies leave the critical path): b1 m and b2 v of the thread's slots
+      float bm[4 * NQ4], bv[4 * NQ4];
 #pragma unroll
       for (int q4 = 0; q4 < NQ4; ++q4) {
-        U.mv4[0][q4][tid] = make_float4(bm[4 * q4], bm[4 * q4 + 1], bm[4 * q4 + 2], bm[4 * q4 + 3]);
-        U.mv4[1][q4][tid] = make_float4(bv[4 * q4], bv[4 * q4 + 1], bv[4 * q4 + 2], bv[4 * q4 + 3]);
+        const float4 a = U.mv4[0][q4][tid], c = U.mv4[1][q4][tid];
+        const xa_f2 b1 = {p.adam.beta1, p.adam.beta1}, b2 = {p.adam.beta2, p.adam.beta2};
+        const xa_f2 m01 = xa_f2{a.x, a.y} * b1, m23 = xa_f2{a.z, a.w} * b1;
+        const xa_f2 v01 = xa_f2{c.x, c.y} * b2, v23 = xa_f2{c.z, c.w} * b2;
+        bm[4 * q4] = m01.x; bm[4 * q4 + 1] = m01.y; bm[4 * q4 + 2] = m23.x; bm[4 * q4 + 3] = m23.y;
+        bv[4 * q4] = v01.x; bv[4 * q4 + 1] = v01.y; bv[4 * q4 + 2] = v23.x; bv[4 * q4 + 3] = v23.y;
       }
-    }
+      {
+        // the thread's g values: 8 W2 pairs (exchange order: pairs 256 h + tid, coalesced) and
+        // its rest pairs, as tagged pairs in one poll
+        constexpr int NG = 8 + RPT;
+        uint32_t off[NG];
+        RowG x[NG];
+#pragma unroll
+        for (int h = 0; h < 8; ++h) off[h] = g_o + (uint32_t)((256 * h + tid) * kRowPB);
+#pragma unroll
+        for (int q = 0; q < RPT; ++q)
+          off[8 + q] = g_o + (uint32_t)((ps.rx[q] >= 0 ? ps.rx[q] / 2 : 0) * kRowPB);
+        bad = !poll_row<NG>(g_r, off, NG, tag, x, ws.ctl, epoch, p.status);
+        XA_STAMP(46);
+#pragma unroll
+        for (int h = 0; h < 8; ++h) {
+          gw[2 * h] = row_v0(x[h]);
+          gw[2 * h + 1] = row_v1(x[h]);
+        }
+#pragma unroll
+        for (int q = 0; q < RPT; ++q)
+          gr[q] = ps.rx[q] >= 0 ? ((ps.rx[q] & 1) ? row_v1(x[8 + q]) : row_v0(x[8 + q])) : 0.0f;
+      }
+      {
+        // the block holds all of g (each parameter on exactly one thread): its own f64 sum of
+        // squares in a fixed thread / wave order, identical in every block
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < 16; q += 2) {
+          s0 = fma((double)gw[q], (double)gw[q], s0);
+          s1 = fma((double)gw[q + 1], (double)gw[q + 1], s1);
+        }
+#pragma unroll
+        for (int q = 0; q < RPT; ++q) s0 = fma((double)gr[q], (double)gr[q], s0);
+        const double ws = xa_wave_sum_f64(s0 + s1);
+        if (lane == 0) U.wsum[w] = ws;
+      }
+      if (__syncthreads_or(bad)) return;
+      XA_STAMP(47);
+      XA_TRACE_PT(b, k, 4);
+#ifndef XA_ABL_CNORM
+      tot = (U.wsum[0] + U.wsum[1]) + (U.wsum[2] + U.wsum[3]);
+      // tf.clip_by_global_norm's scale clip * min(1 / norm, 1 / clip), on the hardware sqrt /
+      // reciprocal units (the update is checked against float64 with a tolerance)
+      const float gn = __builtin_amdgcn_sqrtf((float)tot);
+      const float sc = p.adam.clip_norm > 0.0f
+                           ? p.adam.clip_norm * fminf(frcp(gn), frcp(p.adam.clip_norm)) : 1.0f;
+#else
+      const float sc = (float)tot;
+#endif
+      const float alpha = U.alpha[k];
+#ifndef XA_ABL_ADAM
+      {
+        // m' = b1 m + (1 - b1) sc g, v' = b2 v + (1 - b2) sc^2 g^2 (Keras ApplyAdam on the
+        // clipped gradient sc g, regrouped: the update is checked against float64 with a
+        // tolerance), theta -= alpha m' / (sqrt(v') + eps)
+        const xa_f2 k1 = {sc * omb1, sc * omb1}, k2 = {(sc * sc) * omb2, (sc * sc) * omb2};
+        const xa_f2 al = {alpha, alpha}, ep = {p.adam.eps, p.adam.eps};
+        float th[4 * NQ4];
+#pragma unroll
+        for (int q = 0; q < 4 * NQ4; ++q) th[q] = q < 16 ? wv[q] : q < NS ? rv[q - 16] : 0.0f;
+#pragma unroll
+        for (int q = 0; q < NS; q += 2) {
+          const xa_f2 g = {q < 16 ? gw[q] : gr[q - 16], q + 1 < 16 ? gw[q + 1] : q + 1 < NS ? gr[q + 1 - 16] : 0.0f};
+          const xa_f2 mn = xa_fma2(g, k1, xa_f2{bm[q], bm[q + 1]});
+          const xa_f2 vn = xa_fma2(g * g, k2, xa_f2{bv[q], bv[q + 1]});
+          const xa_f2 step = mn * al;
+          const xa_f2 den = xa_f2{__builtin_amdgcn_sqrtf(vn.x), __builtin_amdgcn_sqrtf(vn.y)} + ep;
+          const xa_f2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+          const xa_f2 tn = xa_fma2(-step, r, xa_f2{th[q], th[q + 1]});
+          th[q] = tn.x;
+          th[q + 1] = tn.y;
+          bm[q] = mn.x;
+          bm[q + 1] = mn.y;
+          bv[q] = vn.x;
+          bv[q + 1] = vn.y;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) wv[q] = th[q];
+#pragma unroll
+        for (int q = 0; q < RPT; ++q) rv[q] = th[16 + q];
+#pragma unroll
+        for (int q4 = 0; q4 < NQ4; ++q4) {
+          U.mv4[0][q4][tid] = make_float4(bm[4 * q4], bm[4 * q4 + 1], bm[4 * q4 + 2], bm[4 * q4 + 3]);
+          U.mv4[1][q4][tid] = make_float4(bv[4 * q4], bv[4 * q4 + 1], bv[4 * q4 + 2], bv[4 * q4 + 3]);
+        }
+      }
 #endif
 #ifndef XA_ABL_LDS
-    ps.to_lds(L, wv, rv);
+      ps.to_lds(L, wv, rv);
 #endif
-    XA_STAMP(43);
-    XA_TRACE_PT(b, k, 5);
+      XA_STAMP(43);
+      XA_TRACE_PT(b, k, 5);
+    }
   }
+#undef XA_OUT
   XA_TRACE_CLK(b, 1);
   XA_TRACE_FLUSH(b);
   // theta / m / v out: every block holds the same final values, so block b stores the
