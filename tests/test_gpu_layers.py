@@ -177,6 +177,94 @@ def test_gemm_transposes_gate_beta_u8(device, M, N, K):
     _close(out.cpu().numpy(), cols @ Wt)
 
 
+# The 32x32-MFMA tile kernel (xa_gemm_shape 22 / 41 / 14) through every operand loader form:
+# (shape, M, N, K, splits, A form, B form, gate + beta). A forms: 'k' / 'm' = f32 k- / m-major,
+# 'k8' / 'm8' = the same from uint8, 'im_m' / 'im_k' = Conv1D im2col on the rows (forward) /
+# on the reduction index (weight gradient); B forms: 'n' / 'k' = n- / k-major.
+# Interior shapes (whole tiles, whole K steps) take the fixed-base fast path; the ragged ones
+# (M, N, K no multiples of 4) the scalar loaders and all three bounds; K = 544 / 548 over 2
+# splits the 16-B run loaders, 548 with a split that ends on a partial K step.
+_TILE_DIMS = {22: [(128, 128, 256), (130, 133, 259)],
+              41: [(256, 64, 256), (257, 37, 259)],
+              14: [(64, 256, 256), (33, 259, 259)]}
+_TILE_CASES = [(shape, M, N, K, 1, af, bf, (af, bf) == ('m', 'k'))
+               for shape, dims in _TILE_DIMS.items() for M, N, K in dims
+               for af in 'km' for bf in 'nk']
+_TILE_CASES += [(22, 128, 128, 544, 2, 'k', 'n', False), (22, 128, 128, 548, 2, 'm', 'k', True)]
+_TILE_CASES += [(22, M, N, K, 1, af, 'n', False)
+                for M, N, K in _TILE_DIMS[22] for af in ('k8', 'm8')]
+_TILE_CASES += [(22, 180, 128, 256, 1, 'im_m', 'n', False),
+                (22, 256, 128, 270, 1, 'im_k', 'n', True)]
+
+
+def _tile_gemm(device, M, N, K, splits, af, bf, gb):
+    """Run one _TILE_CASES GEMM; returns (C on the device, the float64 product)."""
+    from xagents_amd.layers import gemm
+    rng = np.random.default_rng(M + N + K)
+    u8 = af.endswith('8')
+    kw = {}
+    if af.startswith('im'):
+        # rows of W = 20 positions x 64 channels, kernel 4, stride 2 -> P = 9 windows
+        W, Cc, k, s = 20, 64, 4, 2
+        P = (W - k) // s + 1
+        rows = (M if af == 'im_m' else K) // P
+        x = rng.normal(size=(rows, W, Cc)).astype(np.float32)
+        idx = np.arange(P)[:, None] * s + np.arange(k)[None, :]
+        A = x[:, idx, :].reshape(rows * P, k * Cc)
+        if af == 'im_m':
+            kw.update(a_m=(P, W * Cc, s * Cc))
+        else:
+            A = A.T
+            kw.update(a_m=(1, 1, 0), a_k=(P, W * Cc, s * Cc))
+        assert A.shape == (M, K)
+        store = x
+    else:
+        if u8:
+            A = rng.integers(0, 256, size=(M, K), dtype=np.uint8)
+        else:
+            A = rng.normal(size=(M, K)).astype(np.float32)
+        if af[0] == 'k':
+            store = A
+            kw.update(a_m=(1, K, 0))
+        else:
+            store = np.ascontiguousarray(A.T)
+            kw.update(a_m=(1, 1, 0), a_k=(1, M, 0))
+        if u8:
+            A = A.astype(np.float32) / np.float32(255.0)
+    B = rng.normal(size=(K, N)).astype(np.float32)
+    if bf == 'n':
+        bstore = B
+        kw.update(b_ks=N, b_ns=1)
+    else:
+        bstore = np.ascontiguousarray(B.T)
+        kw.update(b_ks=1, b_ns=K)
+    ref = A.astype(np.float64) @ B
+    C0 = rng.normal(size=(M, N)).astype(np.float32)
+    ta, tb = torch.from_numpy(store).to(device), torch.from_numpy(bstore).to(device)
+    C = torch.from_numpy(C0).to(device)
+    if gb:
+        gate = rng.normal(size=(M, N)).astype(np.float32)
+        tg = torch.from_numpy(gate).to(device)
+        kw.update(gate=tg.data_ptr(), ld_gate=N, beta=True)
+        ref = C0 + ref * (gate > 0)
+    ws = torch.empty(splits * M * N + 1, device=device)
+    gemm(M, N, K, ta.data_ptr(), tb.data_ptr(), C.data_ptr(), a_u8=u8, ldc=N, splits=splits,
+         workspace=ws, **kw)
+    torch.cuda.synchronize()
+    return C, ref
+
+
+@pytest.mark.parametrize('shape,M,N,K,splits,af,bf,gb', _TILE_CASES)
+def test_gemm_tile_kernel_operand_forms(device, shape, M, N, K, splits, af, bf, gb):
+    """Every operand form of the grouped-affine loader on the tile kernel (the other GEMM
+    tests reach it almost only with k-major A and n-major B), against the float64 product;
+    the case must run on the kernel it names."""
+    from xagents_amd import _lib
+    assert _lib.load().xa_gemm_shape(M, N, K, splits) == shape
+    C, ref = _tile_gemm(device, M, N, K, splits, af, bf, gb)
+    _close(C.cpu().numpy(), ref)
+
+
 @pytest.mark.parametrize('M', [4, 64, 336])
 def test_gemm_dense_input_gradient_shape(device, M):
     """dX = dZ W^T of the 37632 x 512 dense layer (B read k-major), split as the executor

@@ -29,9 +29,12 @@ def shapes(B):
 
 
 def main():
+    import os
     from xagents_amd import _lib
     from xagents_amd.layers import gemm
     lib = _lib.load()
+    if os.environ.get('XA_LIB'):  # another build of the library instead of the product
+        lib = _lib._lib = _lib.load(os.environ['XA_LIB'])
     dev = torch.device('cuda')
     for B in [int(b) for b in (sys.argv[1:] or ['64', '4096'])]:
         big = torch.randn(B * 84 * 20 * 192, device=dev)  # covers every operand

@@ -16,12 +16,15 @@
 // u8 A operands (Atari frames) are scaled as the reference does,
 // tf.cast(x, f32) / 255.0 (xagents/base.py:505-506).
 //
-// Tiles: 64 x 64 per 256-thread workgroup, 4 waves of 32 x 32 (2 x 2 MFMA tiles),
-// K in steps of 16 staged through double-buffered LDS. K may be split over
-// blockIdx.z; split partial sums are reduced in fixed order by a second kernel that
-// applies the epilogue (deterministic, no atomics).
+// Tiles, per 256-thread workgroup of 4 waves with 2 x 2 MFMA tiles each: 64 x 64 on
+// v_mfma_f32_16x16x4_f32 with K in steps of 16 (gemm_kernel), or 128 x 128 / 256 x 64 /
+// 64 x 256 on v_mfma_f32_32x32x2_f32 with K in steps of 32 (gemm_tile_kernel; pick_shape
+// chooses), both staged through double-buffered LDS. K may be split over blockIdx.z; split
+// partial sums are reduced in fixed order by a second kernel that applies the epilogue
+// (deterministic, no atomics).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/xagents_hip.h"
 #include "xa_adam.hpp"
@@ -1577,30 +1580,24 @@ __global__ __launch_bounds__(256) void conv1d_dgrad_kernel(XaDgradArgs d) {
     }
 }
 
-template <bool AK, bool BNM, bool U8>
-void launch(const XaGemmK& g, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_kernel<AK, BNM, U8>), grid, dim3(256), 0, s, g);
-}
-
-template <int WM, int WN, bool AK, bool BNM, bool U8>
-void launch_tile(const XaGemmK& g, int splits, hipStream_t s) {
-  dim3 grid((g.g.M + 64 * WM - 1) / (64 * WM), (g.g.N + 64 * WN - 1) / (64 * WN), splits);
-  hipLaunchKernelGGL((gemm_tile_kernel<WM, WN, AK, BNM, U8>), grid, dim3(256), 0, s, g);
+// The operand form (A k-major, B n-major, A u8) as the three template booleans of
+// gemm_kernel and gemm_tile_kernel: calls f(std::bool_constant<ak>, <bn>, <u8>)
+template <class F>
+void with_operand_form(bool ak, bool bn, bool u8, F&& f) {
+  auto pick = [](bool v, auto&& k) { v ? k(std::true_type{}) : k(std::false_type{}); };
+  pick(ak, [&](auto AK) {
+    pick(bn, [&](auto BNM) { pick(u8, [&](auto U8) { f(AK, BNM, U8); }); });
+  });
 }
 
 template <int WM, int WN>
-void dispatch_tile(const XaGemmK& g, bool ak, bool bn, bool u8, hipStream_t s) {
-  if (u8) {
-    if (ak && bn) launch_tile<WM, WN, true, true, true>(g, g.g.splits, s);
-    else if (ak) launch_tile<WM, WN, true, false, true>(g, g.g.splits, s);
-    else if (bn) launch_tile<WM, WN, false, true, true>(g, g.g.splits, s);
-    else launch_tile<WM, WN, false, false, true>(g, g.g.splits, s);
-  } else {
-    if (ak && bn) launch_tile<WM, WN, true, true, false>(g, g.g.splits, s);
-    else if (ak) launch_tile<WM, WN, true, false, false>(g, g.g.splits, s);
-    else if (bn) launch_tile<WM, WN, false, true, false>(g, g.g.splits, s);
-    else launch_tile<WM, WN, false, false, false>(g, g.g.splits, s);
-  }
+void launch_tile(const XaGemmK& g, bool ak, bool bn, bool u8, hipStream_t s) {
+  dim3 grid((g.g.M + 64 * WM - 1) / (64 * WM), (g.g.N + 64 * WN - 1) / (64 * WN), g.g.splits);
+  with_operand_form(ak, bn, u8, [&](auto AK, auto BNM, auto U8) {
+    hipLaunchKernelGGL(
+        (gemm_tile_kernel<WM, WN, decltype(AK)::value, decltype(BNM)::value, decltype(U8)::value>),
+        grid, dim3(256), 0, s, g);
+  });
 }
 
 // kernel for a GEMM: 0 = 64 x 64 small-tile, 22 / 41 / 14 = tile kernel (WM, WN),
@@ -1852,19 +1849,15 @@ static void launch_main(const XaGemmArgs& g, hipStream_t s) {
     dim3 gs((g.M + 31) / 32, (g.N + 31) / 32, g.splits);
     if (u8) hipLaunchKernelGGL(gemm_skinny_kernel<true>, gs, dim3(64), 0, s, g);
     else hipLaunchKernelGGL(gemm_skinny_kernel<false>, gs, dim3(64), 0, s, g);
-  } else if (shape == 22) dispatch_tile<2, 2>(kg, ak, bn, u8, s);
-  else if (shape == 41) dispatch_tile<4, 1>(kg, ak, bn, u8, s);
-  else if (shape == 14) dispatch_tile<1, 4>(kg, ak, bn, u8, s);
-  else if (u8) {
-    if (ak && bn) launch<true, true, true>(kg, grid, s);
-    else if (ak) launch<true, false, true>(kg, grid, s);
-    else if (bn) launch<false, true, true>(kg, grid, s);
-    else launch<false, false, true>(kg, grid, s);
-  } else {
-    if (ak && bn) launch<true, true, false>(kg, grid, s);
-    else if (ak) launch<true, false, false>(kg, grid, s);
-    else if (bn) launch<false, true, false>(kg, grid, s);
-    else launch<false, false, false>(kg, grid, s);
+  } else if (shape == 22) launch_tile<2, 2>(kg, ak, bn, u8, s);
+  else if (shape == 41) launch_tile<4, 1>(kg, ak, bn, u8, s);
+  else if (shape == 14) launch_tile<1, 4>(kg, ak, bn, u8, s);
+  else {
+    with_operand_form(ak, bn, u8, [&](auto AK, auto BNM, auto U8) {
+      hipLaunchKernelGGL(
+          (gemm_kernel<decltype(AK)::value, decltype(BNM)::value, decltype(U8)::value>), grid,
+          dim3(256), 0, s, kg);
+    });
   }
 }
 
