@@ -1,6 +1,7 @@
 """Direct GPU tests of the small single-launch kernels that the agents' tests reach only at
 one shape each: the row-dot head backward (xa_head_bwd, gemm.hip), the TRPO helpers
-(trpo.hip) and the byte movers / elementwise helpers of offpolicy.hip.
+(trpo.hip), the byte movers / elementwise helpers of offpolicy.hip and its TD heads, greedy
+action and action noise (the arithmetic of td_terms.hpp).
 
 Every kernel is called through the C ABI with raw pointers and compared with a numpy
 float64 (or exact byte) reference of the same operation. Tolerances are bit equality, a
@@ -634,3 +635,230 @@ def test_activation_grad_exact(device, n, act, in_place):
     _assert_bits_equal(_host(ty), y, 'y')
     if not in_place:
         _assert_bits_equal(_host(tdy).reshape(-1)[:n], dy, 'dy')
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. the off-policy TD heads, the greedy action and the action noise (csrc/td_terms.hpp)
+# ---------------------------------------------------------------------------------------------
+_TD_B = 70                 # one full 64-thread block and a ragged one
+_DELTA = F32(0.5)
+
+
+def _np_td_term(e, delta):
+    """td_terms.hpp td_term in f32 numpy, one rounding per operation in its order."""
+    if delta > 0:
+        d = np.minimum(np.maximum(e, -delta), delta)
+        ae = np.abs(e)
+        return d, np.where(ae <= delta, F32(0.5) * (e * e), delta * (ae - F32(0.5) * delta))
+    return F32(2.0) * e, e * e
+
+
+def _exact_error_rows(B):
+    """(values, targets' rewards) for the first rows of a batch whose samples are done, so
+    y = r exactly: errors v - r of 0, +-0.25, +-0.5 (= delta exactly) and +-0.75."""
+    e = np.array([0.0, 0.25, -0.25, 0.5, -0.5, 0.75, -0.75], F32)
+    r = np.array([1.0, -2.0, 0.25, 3.5, -0.75, 2.0, 0.5], F32)
+    assert e.size <= B
+    return r + e, r
+
+
+@pytest.mark.parametrize('huber', [F32(0.0), _DELTA])
+@pytest.mark.parametrize('twin', [False, True])
+def test_critic_td_grad_exact(device, twin, huber):
+    """xa_critic_td_grad, single (DDPG) and twin (TD3), MSE and Huber(0.5): dv1, dv2 and the
+    per-sample loss bit-identical to the f32 numpy restatement of td_terms.hpp (nothing is
+    contracted in the build). Dones of 0 and 1, errors on both sides of +-delta and exactly
+    on it; the rows after every output stay untouched."""
+    L = _lib()
+    B = _TD_B
+    rng = np.random.default_rng(17 + 2 * int(twin))
+    v1, v2, tv1, tv2, rew = (rng.normal(size=B).astype(F32) for _ in range(5))
+    done = (rng.random(B) < 0.3).astype(F32)
+    gamma = F32(0.99)
+    ve, re_ = _exact_error_rows(B)
+    k = ve.size
+    v1[:k], rew[:k], done[:k] = ve, re_, 1.0
+    v2[:k] = (re_ - (ve - re_))                       # the mirrored errors for the twin
+    assert (done == 0).any() and (done == 1).any()
+    tv = np.minimum(tv1, tv2) if twin else tv1
+    y = rew + ((F32(1.0) - done) * gamma) * tv
+    assert y.dtype == F32 and ((np.abs(v1 - y) == _DELTA).any())
+    assert (np.abs(v1 - y) < _DELTA).any() and (np.abs(v1 - y) > _DELTA).any()
+    d1, loss = _np_td_term(v1 - y, huber)
+    if twin:
+        d2, l2 = _np_td_term(v2 - y, huber)
+        loss = loss + l2
+    t = {n: _dev(a, device) for n, a in dict(v1=v1, v2=v2, tv1=tv1, tv2=tv2, rew=rew,
+                                             done=done).items()}
+    out = {n: torch.full((B + 2,), float(CANARY), device=device) for n in ('dv1', 'dv2', 'loss')}
+    L.call('xa_critic_td_grad', t['v1'].data_ptr(), t['v2'].data_ptr() if twin else None,
+           t['tv1'].data_ptr(), t['tv2'].data_ptr() if twin else None, t['rew'].data_ptr(),
+           t['done'].data_ptr(), B, float(gamma), float(huber), out['dv1'].data_ptr(),
+           out['dv2'].data_ptr() if twin else None, out['loss'].data_ptr(), L.stream())
+    tag = f'twin{int(twin)} huber{huber}'
+    h = {n: _host(b) for n, b in out.items()}
+    _assert_bits_equal(h['dv1'][:B], d1.astype(F32), f'{tag}: dv1')
+    _assert_bits_equal(h['loss'][:B], loss.astype(F32), f'{tag}: loss')
+    if twin:
+        _assert_bits_equal(h['dv2'][:B], d2.astype(F32), f'{tag}: dv2')
+    else:
+        assert (h['dv2'] == CANARY).all()
+    for n, b in h.items():
+        assert (b[B:] == CANARY).all(), f'{tag}: wrote past the end of {n}'
+
+
+def _dqn_rows(B, A, seed):
+    """Q rows with tied maxima (pairs and whole rows) among random ones."""
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(B, A)).astype(F32)
+    q[0::5, 2] = q[0::5, 1] = q[0::5].max(1) + F32(0.5)     # the maximum at 1 and 2
+    q[3::10] = F32(0.25)                                    # every entry tied
+    return q
+
+
+@pytest.mark.parametrize('huber', [F32(0.0), _DELTA])
+@pytest.mark.parametrize('double', [False, True])
+@pytest.mark.parametrize('A', [3, 6])
+def test_dqn_td_grad_exact(device, A, double, huber):
+    """xa_dqn_td_grad, plain and double, MSE and Huber(0.5): dq (zero off the action) and the
+    per-sample loss bit-identical to the f32 numpy restatement of td_terms.hpp. Tied maxima in
+    the online next-state rows (the first index selects the target value), done rows, errors
+    on both sides of +-delta and exactly on it. The optimizer step counter goes up by exactly
+    1 when passed and nothing is bumped when it is NULL."""
+    L = _lib()
+    B = _TD_B
+    rng = np.random.default_rng(100 * A + 2 * int(double))
+    q = rng.normal(size=(B, A)).astype(F32)
+    qt = rng.normal(size=(B, A)).astype(F32)
+    qo = _dqn_rows(B, A, A)
+    act = rng.integers(0, A, size=B).astype(np.int32)
+    rew = rng.normal(size=B).astype(F32)
+    done = (rng.random(B) < 0.3).astype(F32)
+    gamma = F32(0.99)
+    ve, re_ = _exact_error_rows(B)
+    k = ve.size
+    rew[:k], done[:k] = re_, 1.0
+    q[np.arange(k), act[:k]] = ve
+    rows = np.arange(B)
+    if double:
+        best = np.argmax(qo, 1)                        # numpy: the first maximum
+        assert (best[0::5] == 1).all() and (best[3::10] == 0).all()
+        assert (qt[0::5, 1] != qt[0::5, 2]).all()      # the second index would show
+        v = qt[rows, best]
+    else:
+        v = qt.max(1)
+    v = np.where(done != 0, F32(0.0), v)
+    y = v * gamma + rew
+    diff = y - q[rows, act]
+    assert diff.dtype == F32 and (np.abs(diff) == _DELTA).any()
+    assert (np.abs(diff) < _DELTA).any() and (np.abs(diff) > _DELTA).any()
+    d, l = _np_td_term(diff, huber)
+    want_dq = np.zeros((B, A), F32)
+    want_dq[rows, act] = -d / F32(A)
+    want_l = (l / F32(A)).astype(F32)
+    t = {n: _dev(a, device) for n, a in dict(q=q, qt=qt, qo=qo, act=act, rew=rew,
+                                             done=done).items()}
+    step = torch.full((2,), 7, dtype=torch.int32, device=device)
+    tag = f'A{A} double{int(double)} huber{huber}'
+    for with_step in (True, False):
+        dq = _dev(_with_canary(np.full((B, A), CANARY, F32)), device)
+        loss = torch.full((B + 2,), float(CANARY), device=device)
+        L.call('xa_dqn_td_grad', t['q'].data_ptr(), t['qt'].data_ptr(),
+               t['qo'].data_ptr() if double else None, t['act'].data_ptr(),
+               t['rew'].data_ptr(), t['done'].data_ptr(), B, A, float(gamma), float(huber),
+               dq.data_ptr(), loss.data_ptr(), step.data_ptr() if with_step else None,
+               L.stream())
+        dqh, lh = _host(dq), _host(loss)
+        _assert_bits_equal(dqh[:B], want_dq, f'{tag}: dq')
+        _assert_bits_equal(lh[:B], want_l, f'{tag}: loss')
+        assert (dqh[B:] == CANARY).all() and (lh[B:] == CANARY).all()
+        assert _host(step).tolist() == [8, 7], f'{tag}: adam_step (passed: {with_step})'
+
+
+@pytest.mark.parametrize('A', [3, 6])
+def test_dqn_act_first_argmax_and_random(device, A):
+    """xa_dqn_act: the first index of each row's maximum (tied pairs, rows tied throughout),
+    and with use_random the given actions (q is not needed then)."""
+    L = _lib()
+    n = _TD_B
+    q = _dqn_rows(n, A, 7 * A)
+    want = np.argmax(q, 1).astype(np.int32)
+    assert (want[0::5] == 1).all() and (want[3::10] == 0).all()
+    tq = _dev(q, device)
+    given = np.random.default_rng(A).integers(0, A, size=n).astype(np.int32)
+    tg = _dev(given, device)
+    for use_random, ref in ((0, want), (1, given)):
+        out = torch.full((n + 2,), -5, dtype=torch.int32, device=device)
+        L.call('xa_dqn_act', None if use_random else tq.data_ptr(), n, A, tg.data_ptr(),
+               use_random, out.data_ptr(), L.stream())
+        oh = _host(out)
+        np.testing.assert_array_equal(oh[:n], ref)
+        assert (oh[n:] == -5).all()
+    np.testing.assert_array_equal(_host(tg), given)
+
+
+_NA_ROWS, _NA_COLS, _NA_LDX, _NA_LDO = 5, 3, 5, 4
+_NA_CTR, _NA_SEED = (3 << 32) | 5, (0x9E3779B9 << 32) | 0x7F4A7C15
+
+
+def _np_philox_normal(rows, cols, ctr, seed):
+    """td_terms.hpp philox_normal at (row, col, ctr, seed) in float64: u1, u2 formed exactly
+    from the oracle's Philox words, the angle rounded to f32 as the kernel's product is."""
+    import oracle
+    out = np.zeros((rows, cols))
+    for b in range(rows):
+        for a in range(cols):
+            r = oracle.philox([b, a, ctr & 0xffffffff, ctr >> 32],
+                              [seed & 0xffffffff, seed >> 32])
+            u1 = (float(int(r[0]) >> 8) + 1.0) * 2.0 ** -24
+            u2 = float(int(r[1]) >> 8) * 2.0 ** -24
+            angle = float(F32(6.283185307179586) * F32(u2))
+            out[b, a] = np.sqrt(-2.0 * np.log(u1)) * np.cos(angle)
+    return out
+
+
+def _noisy(L, device, x, sigma, clip, lo, hi, ctr):
+    tx = _dev(x, device)
+    out = torch.full((_NA_ROWS + 1, _NA_LDO), float(CANARY), device=device)
+    noise = torch.full((_NA_ROWS + 1, _NA_COLS), float(CANARY), device=device)
+    L.call('xa_noisy_actions', tx.data_ptr(), _NA_LDX, _NA_ROWS, _NA_COLS, float(sigma),
+           float(clip), float(lo), float(hi), ctr.data_ptr() if ctr is not None else None,
+           _NA_SEED, out.data_ptr(), _NA_LDO, noise.data_ptr(), L.stream())
+    oh, nh = _host(out), _host(noise)
+    assert (oh[_NA_ROWS:] == CANARY).all() and (oh[:, _NA_COLS:] == CANARY).all()
+    assert (nh[_NA_ROWS:] == CANARY).all()
+    _assert_bits_equal(_host(tx), x, 'noisy_actions: the input')
+    return oh[:_NA_ROWS, :_NA_COLS], nh[:_NA_ROWS]
+
+
+def test_noisy_actions_vs_philox_f64(device):
+    """xa_noisy_actions on 5 x 3 with leading dimensions wider than the columns: the stored
+    noise against sigma N(0, 1) from the oracle's Philox at the same (row, col, counter, seed)
+    in float64, at test_fused_step_actions_vs_f64's atol for this path; out is exactly
+    clip(x + stored noise, lo, hi) in f32. With a finite noise_clip no stored element exceeds
+    it and some sit exactly on it. sigma = 0 stores exact zeros whatever the counter holds
+    (or without one)."""
+    L = _lib()
+    rng = np.random.default_rng(3)
+    x = rng.uniform(-1, 1, size=(_NA_ROWS, _NA_LDX)).astype(F32)
+    sigma, lo, hi = F32(0.2), F32(-1.0), F32(1.0)
+    ctr = _dev(np.array([_NA_CTR], np.int64), device)
+    normal = _np_philox_normal(_NA_ROWS, _NA_COLS, _NA_CTR, _NA_SEED)
+    assert normal.std() > 0.5
+    xs = x[:, :_NA_COLS]
+    for clip in (F32(np.inf), F32(0.1)):
+        out, nz = _noisy(L, device, x, sigma, clip, lo, hi, ctr)
+        raw = normal * float(sigma)
+        np.testing.assert_allclose(nz, np.clip(raw, -float(clip), float(clip)), rtol=0,
+                                   atol=1e-5)
+        _assert_bits_equal(out, np.minimum(np.maximum(xs + nz, lo), hi), f'clip {clip}: out')
+        if np.isfinite(clip):
+            over = np.abs(raw) > float(clip) + 1e-4
+            assert over.any() and (~over).any()
+            assert (np.abs(nz) <= clip).all() and (np.abs(nz[over]) == clip).all()
+    assert int(_host(ctr)[0]) == _NA_CTR                 # the kernel only reads the counter
+    other = _dev(np.array([_NA_CTR + 1], np.int64), device)
+    for c in (ctr, other, None):
+        out, nz = _noisy(L, device, x, F32(0.0), F32(0.1), lo, hi, c)
+        _assert_bits_equal(nz, np.zeros((_NA_ROWS, _NA_COLS), F32), 'sigma 0: noise')
+        _assert_bits_equal(out, np.minimum(np.maximum(xs, lo), hi), 'sigma 0: out')

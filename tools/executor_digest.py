@@ -31,7 +31,8 @@ DEV = 'cuda:0'
 STEPS = 4
 BUFFERS = ('obs_buf', 'b_act', 'b_logp', 'b_val', 'b_ent', 'b_rew', 'b_done', 'b_epret',
            'b_ret', 'next_val', 'batch_states', 'g_act', 'g_mu', 'g_rew', 'g_done', 'r_frames',
-           'r_mu', 'r_act', 'r_rew', 'r_done', 's_frames', 's_mu', 's_act', 's_rew', 's_done')
+           'r_mu', 'r_act', 'r_rew', 'r_done', 's_frames', 's_mu', 's_act', 's_rew', 's_done',
+           'dq', 'td_loss', 'dv1', 'dv2', 'critic_loss', 'noise')
 
 
 def seed_host(s):
@@ -64,7 +65,12 @@ def acer(use_graph):
                 replay_ratio=2, grad_norm=10.0, use_graph=use_graph)
 
 
-def dqn(learn_graph):
+def dqn(learn_graph, fused_head=True, **agent_kw):
+    # XA_DQN_FUSED_HEAD=0: xa_dqn_act / xa_dqn_td_grad launches instead of xa_dqn_head
+    if fused_head:
+        os.environ.pop('XA_DQN_FUSED_HEAD', None)
+    else:
+        os.environ['XA_DQN_FUSED_HEAD'] = '0'
     if learn_graph:
         os.environ['XA_DQN_LEARN_GRAPH'] = '1'
     else:
@@ -72,12 +78,18 @@ def dqn(learn_graph):
     envs = create_envs('PongNoFrameskip-v4', 2, device=DEV, seed=3)
     model = create_model(envs, 'dqn', 'model', seed=9, device=DEV)
     agent = DQN(envs, model, create_buffers('dqn', 40, 4, 2, initial_size=20), seed=2,
-                quiet=True, epsilon_decay_steps=20, target_sync_steps=3)
+                quiet=True, epsilon_decay_steps=20, target_sync_steps=3, **agent_kw)
     agent.fill_buffers()
     return agent
 
 
-def ddpg(kind):
+def ddpg(kind, fused=True, **agent_kw):
+    # XA_TD3_FUSED=0: the layer executor with xa_critic_td_grad, xa_noisy_actions and xa_polyak
+    # instead of the persistent xa_td3_update / xa_td3_act launches
+    if fused:
+        os.environ.pop('XA_TD3_FUSED', None)
+    else:
+        os.environ['XA_TD3_FUSED'] = '0'
     n = 4
     envs = create_envs('BipedalWalker-v3', n, mode='dynamics', device=DEV, seed=4)
     kw = dict(seed=7, device=DEV, optimizer_kwargs=dict(learning_rate=1e-3))
@@ -85,7 +97,7 @@ def ddpg(kind):
     critic = create_model(envs, kind, 'critic_model', **kw)
     bufs = create_buffers(kind, 64 * n, 2 * n, n, initial_size=8 * n)
     agent = (TD3 if kind == 'td3' else DDPG)(envs, actor, critic, bufs, seed=3, quiet=True,
-                                             gradient_steps=1)
+                                             gradient_steps=1, **agent_kw)
     agent.fill_buffers()
     return agent
 
@@ -108,8 +120,17 @@ CASES = [
     ('acer_pong_eager', lambda: acer(False)),
     ('dqn_pong_learn_graph', lambda: dqn(True)),
     ('dqn_pong_direct', lambda: dqn(False)),
+    ('dqn_pong_double', lambda: dqn(True, double=True)),
+    ('dqn_pong_huber', lambda: dqn(True, huber_delta=0.5)),
+    ('dqn_pong_executor', lambda: dqn(True, fused_head=False)),
+    ('dqn_pong_executor_double_huber', lambda: dqn(True, fused_head=False, double=True,
+                                                   huber_delta=0.5)),
     ('td3_walker', lambda: ddpg('td3')),
     ('ddpg_walker', lambda: ddpg('ddpg')),
+    ('td3_walker_huber', lambda: ddpg('td3', huber_delta=0.5)),
+    ('td3_walker_executor', lambda: ddpg('td3', fused=False)),
+    ('ddpg_walker_executor', lambda: ddpg('ddpg', fused=False)),
+    ('td3_walker_executor_huber', lambda: ddpg('td3', fused=False, huber_delta=0.5)),
 ]
 
 

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "../../include/xagents_hip.h"
+#include "td_terms.hpp"
 #include "xa_adam.hpp"
 #include "xa_common.hpp"
 
@@ -51,9 +52,7 @@ XA_DEV int64_t grouped(int i, int p, int64_t r, int64_t s) {
 
 XA_DEV float epilogue(float v, int n, const XaGemmArgs& g) {
   if (g.bias) v = v + g.bias[n];
-  if (g.act == XA_ACT_RELU) v = fmaxf(v, 0.0f);
-  else if (g.act == XA_ACT_TANH) v = xa_tanhf(v);
-  return v;
+  return xa_td::act(v, g.act);
 }
 
 XA_DEV void store_c(float v, int m, int n, const XaGemmArgs& g) {
@@ -772,8 +771,8 @@ __global__ __launch_bounds__(256) void gemm_rowdot_kernel(XaGemmArgs g) {
 // DQN's per-row heads fused into the Q head's row-dot launch (one launch fewer per use):
 // mode 0 (act, dqn/agent.py:107-116): actions[m] = first argmax of the row's Q values;
 // mode 1 (TD, dqn/agent.py:118-171): the head is the TARGET network's, row b = sample b:
-// exactly xa_dqn_td_grad's arithmetic (offpolicy.hip dqn_td_kernel) with Qt(s') taken from
-// the lanes instead of memory; the optimizer step bump rides along
+// xa_dqn_td_grad's step (offpolicy.hip dqn_td_kernel; both call td_terms.hpp) with Qt(s')
+// taken from the lanes instead of memory; the optimizer step bump rides along
 XA_DEV void dqn_row_step(const XaGemmArgs& g, const XaDqnHeadArgs& d, int m, int lane, float v);
 
 __global__ __launch_bounds__(256) void dqn_head_kernel(XaGemmArgs g, XaDqnHeadArgs d) {
@@ -809,14 +808,7 @@ XA_DEV void dqn_row_step(const XaGemmArgs& g, const XaDqnHeadArgs& d, int m, int
   const int b = m;
   float vn;
   if (d.q_next_online) {
-    const float* qo = d.q_next_online + (int64_t)b * A;
-    int best = 0;
-    float bv = qo[0];
-    for (int a = 1; a < A; ++a)
-      if (qo[a] > bv) {
-        bv = qo[a];
-        best = a;
-      }
+    const int best = xa_td::argmax_first(d.q_next_online + (int64_t)b * A, A);
     vn = qv[0];
 #pragma unroll
     for (int a = 1; a < RD_MAXN; ++a)
@@ -827,19 +819,10 @@ XA_DEV void dqn_row_step(const XaGemmArgs& g, const XaDqnHeadArgs& d, int m, int
     for (int a = 1; a < RD_MAXN; ++a)
       if (a < A) vn = fmaxf(vn, qv[a]);
   }
-  if (d.dones[b] != 0.0f) vn = 0.0f;
-  const float y = vn * d.gamma + d.rewards[b];
+  const float y = xa_td::dqn_target(vn, d.dones[b], d.gamma, d.rewards[b]);
   const int ab = d.act[b];
-  const float diff = y - d.q[(int64_t)b * A + ab];
   float dqa, l;
-  if (d.huber > 0.0f) {
-    const float ad = fabsf(diff);
-    dqa = -fminf(fmaxf(diff, -d.huber), d.huber) / (float)A;
-    l = (ad <= d.huber ? 0.5f * (diff * diff) : d.huber * (ad - 0.5f * d.huber)) / (float)A;
-  } else {
-    dqa = (-2.0f * diff) / (float)A;
-    l = (diff * diff) / (float)A;
-  }
+  xa_td::dqn_td(y - d.q[(int64_t)b * A + ab], d.huber, A, dqa, l);
   if (lane < A) d.dq[(int64_t)b * A + lane] = lane == ab ? dqa : 0.0f;
   if (lane == 0 && d.loss) d.loss[b] = l;
 }

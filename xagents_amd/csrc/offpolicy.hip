@@ -10,6 +10,7 @@
 //     the bytes.
 #include "../../include/xagents_hip.h"
 #include "env_step.hpp"
+#include "td_terms.hpp"
 #include "xa_common.hpp"
 
 namespace {
@@ -53,21 +54,12 @@ __global__ void dqn_act_kernel(const float* __restrict__ q, int n, int A,
     actions[i] = random_actions[i];
     return;
   }
-  const float* r = q + (size_t)i * A;
-  int best = 0;
-  float bv = r[0];
-  for (int a = 1; a < A; ++a)
-    if (r[a] > bv) {
-      bv = r[a];
-      best = a;
-    }
-  actions[i] = best;
+  actions[i] = xa_td::argmax_first(q + (size_t)i * A, A);
 }
 
-// DQN.get_targets + the MSE gradient (dqn/agent.py:118-171):
-//   v' = double ? Qt(s')[argmax Q(s')] : max_a Qt(s');  v' = 0 where done
-//   y_b = v' gamma + r_b;   L = sum_b mean_a (y - Q)^2 (minimize on a [B] loss sums)
-//   dQ[b][a_b] = -2 (y_b - Q[b][a_b]) / A, zero elsewhere (y copies Q off the action)
+// DQN.get_targets + the loss gradient (dqn/agent.py:118-171), td_terms.hpp's dqn_target and
+// dqn_td on v' = double ? Qt(s')[argmax Q(s')] : max_a Qt(s') (minimize on a [B] loss sums);
+// dQ is zero off the action (y copies Q there)
 __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restrict__ q_next_t,
                               const float* __restrict__ q_next_o, const int* __restrict__ act,
                               const float* __restrict__ rew, const float* __restrict__ done,
@@ -79,33 +71,15 @@ __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restri
   const float* qt = q_next_t + (size_t)b * A;
   float v;
   if (q_next_o) {
-    const float* qo = q_next_o + (size_t)b * A;
-    int best = 0;
-    float bv = qo[0];
-    for (int a = 1; a < A; ++a)
-      if (qo[a] > bv) {
-        bv = qo[a];
-        best = a;
-      }
-    v = qt[best];
+    v = qt[xa_td::argmax_first(q_next_o + (size_t)b * A, A)];
   } else {
     v = qt[0];
     for (int a = 1; a < A; ++a) v = fmaxf(v, qt[a]);
   }
-  if (done[b] != 0.0f) v = 0.0f;
-  const float y = v * gamma + rew[b];
+  const float y = xa_td::dqn_target(v, done[b], gamma, rew[b]);
   const int ab = act[b];
-  const float diff = y - q[(size_t)b * A + ab];
   float dqa, l;
-  if (huber > 0.0f) {
-    // tf.keras.losses.Huber(delta): 0.5 x^2 if |x| <= delta else delta (|x| - 0.5 delta)
-    const float ad = fabsf(diff);
-    dqa = -fminf(fmaxf(diff, -huber), huber) / (float)A;
-    l = (ad <= huber ? 0.5f * (diff * diff) : huber * (ad - 0.5f * huber)) / (float)A;
-  } else {
-    dqa = (-2.0f * diff) / (float)A;
-    l = (diff * diff) / (float)A;
-  }
+  xa_td::dqn_td(y - q[(size_t)b * A + ab], huber, A, dqa, l);
   for (int a = 0; a < A; ++a) dq[(size_t)b * A + a] = a == ab ? dqa : 0.0f;
   if (loss) loss[b] = l;
 }
@@ -166,28 +140,23 @@ __global__ __launch_bounds__(256) void ring_gather_fields_kernel(XaGatherArgs a)
   }
 }
 
-// y = (1 - tau) y + tau x (DDPG.sync_target_models, ddpg/agent.py:73-85); tau = 1: copy
+// the Polyak blend of y towards x (td_terms.hpp polyak) over a parameter vector
 __global__ __launch_bounds__(256) void polyak_kernel(const float* __restrict__ x,
                                                      float* __restrict__ y, int64_t n,
                                                      float tau) {
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
-    y[e] = tau == 1.0f ? x[e] : (1.0f - tau) * y[e] + tau * x[e];
+    y[e] = xa_td::polyak(y[e], x[e], tau);
 }
 
 __global__ void step_bump_kernel(int* step) { step[0] += 1; }
 
-// dz = dy * act'(y) from the layer output y (relu: y > 0; tanh: 1 - y^2); dz may be dy
-// (the layer executor's in-place calls), so that pair carries no __restrict__
+// dz = dy * act'(y) from the layer output y (td_terms.hpp act_grad); dz may be dy (the
+// layer executor's in-place calls), so that pair carries no __restrict__
 __global__ __launch_bounds__(256) void act_grad_kernel(const float* __restrict__ y,
                                                        const float* dy, int64_t n, int act,
                                                        float* dz) {
-  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const float v = y[e];
-    float d = dy[e];
-    if (act == XA_ACT_RELU) d = v > 0.0f ? d : 0.0f;
-    else if (act == XA_ACT_TANH) d = d * (1.0f - v * v);
-    dz[e] = d;
-  }
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+    dz[e] = xa_td::act_grad(dy[e], y[e], act);
 }
 
 // ---- off-policy replay env step + ring store (BaseAgent.step_envs with
@@ -266,17 +235,8 @@ __global__ __launch_bounds__(256) void copy_block_kernel(const float* __restrict
   }
 }
 
-// standard normal from Philox4x32-10 (Box-Muller on two 24-bit uniforms in (0, 1])
-XA_DEV float philox_normal(uint32_t i, uint32_t j, uint64_t ctr, uint64_t seed) {
-  const xa_u4 r = xa_philox(i, j, (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed,
-                            (uint32_t)(seed >> 32));
-  const float u1 = ((float)(r.x >> 8) + 1.0f) * 5.9604644775390625e-08f;
-  const float u2 = (float)(r.y >> 8) * 5.9604644775390625e-08f;
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
-
-// out[b][a] = clip(x[b][a] + clip(sigma N(0,1), -noise_clip, noise_clip), lo, hi)
-// TD3 target smoothing (td3/agent.py:83-91) and DDPG exploration (ddpg/agent.py:60-71)
+// out[b][a] = clip(x[b][a] + noise, lo, hi), the noise td_terms.hpp's clipped_noise at
+// (b, a): TD3 target smoothing (td3/agent.py:83-91), DDPG exploration (ddpg/agent.py:60-71)
 __global__ void noisy_actions_kernel(const float* __restrict__ x, int64_t ld_x, int rows,
                                      int cols, float sigma, float noise_clip, float lo, float hi,
                                      const uint64_t* __restrict__ ctr, uint64_t seed,
@@ -285,18 +245,16 @@ __global__ void noisy_actions_kernel(const float* __restrict__ x, int64_t ld_x, 
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= rows * cols) return;
   const int b = e / cols, a = e % cols;
-  float n = 0.0f;
-  if (sigma != 0.0f) {
-    n = philox_normal((uint32_t)b, (uint32_t)a, ctr ? *ctr : 0ull, seed) * sigma;
-    n = fminf(fmaxf(n, -noise_clip), noise_clip);
-  }
+  // (sigma == 0 draws nothing: the counter is not read either)
+  const float n = sigma != 0.0f ? xa_td::clipped_noise((uint32_t)b, (uint32_t)a, ctr ? *ctr : 0ull,
+                                                       seed, sigma, noise_clip)
+                                : 0.0f;
   if (noise_out) noise_out[e] = n;
   out[(int64_t)b * ld_out + a] = fminf(fmaxf(x[(int64_t)b * ld_x + a] + n, lo), hi);
 }
 
-// DDPG / TD3 critic targets and MSE gradients (ddpg/agent.py:104-127, td3/agent.py:66-110):
-//   y = r + ((1 - d) gamma) min(tv1, tv2);  dv_i = 2 (v_i - y)  (MSE over a size-1 axis,
-//   minimize sums over the batch); loss_i[b] = (v_i - y)^2
+// DDPG / TD3 critic targets and loss gradients: td_terms.hpp's critic_target on min(tv1, tv2)
+// and its td_term per critic (minimize sums over the batch); loss[b] is the twins' sum
 __global__ void critic_td_kernel(const float* __restrict__ v1, const float* __restrict__ v2,
                                  const float* __restrict__ tv1, const float* __restrict__ tv2,
                                  const float* __restrict__ rew, const float* __restrict__ done,
@@ -305,24 +263,13 @@ __global__ void critic_td_kernel(const float* __restrict__ v1, const float* __re
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const float tv = tv2 ? fminf(tv1[b], tv2[b]) : tv1[b];
-  const float y = rew[b] + ((1.0f - done[b]) * gamma) * tv;
-  // MSE (the reference): d = 2 e, l = e^2; Huber(delta) opt-in: d = clip(e, +-delta),
-  // l = 0.5 e^2 if |e| <= delta else delta (|e| - 0.5 delta)
-  auto term = [huber](float e, float& d) {
-    if (huber > 0.0f) {
-      d = fminf(fmaxf(e, -huber), huber);
-      const float ae = fabsf(e);
-      return ae <= huber ? 0.5f * (e * e) : huber * (ae - 0.5f * huber);
-    }
-    d = 2.0f * e;
-    return e * e;
-  };
+  const float y = xa_td::critic_target(rew[b], done[b], gamma, tv);
   float d1;
-  float l = term(v1[b] - y, d1);
+  float l = xa_td::td_term(v1[b] - y, huber, d1);
   dv1[b] = d1;
   if (v2) {
     float d2;
-    l = l + term(v2[b] - y, d2);
+    l = l + xa_td::td_term(v2[b] - y, huber, d2);
     dv2[b] = d2;
   }
   if (loss) loss[b] = l;

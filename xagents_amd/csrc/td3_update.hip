@@ -23,8 +23,8 @@
 //       the last job of a row tile finishes L3: target actor tanh (+ TD3 smoothing noise,
 //       clip) -> a'; critics -> v1, v2; actor tanh -> pi(s)
 //   P4  target critics L1 on [s', a'];  P5  L2 (+ the L3 partials; the row tile's last job
-//       runs the TD head y = r + (1 - d) gamma min(tv1, tv2), dv = 2 (v - y) (MSE) or
-//       clip(v - y, +-delta) (opt-in Huber), per-sample loss)
+//       runs the TD head: td_terms.hpp's critic_target on min(tv1, tv2) and its td_term per
+//       critic (MSE or opt-in Huber), per-sample loss)
 //   P7  critics backward: dW2 / db2 (dZ2 = dv W3^T gate(h2) formed while staging), dH1,
 //       dW3 / db3
 //   P8  critics: dW1 / db1 with the Keras Adam step applied in the same job, Adam of every
@@ -45,11 +45,13 @@
 #include <math.h>
 
 #include "../../include/xagents_hip.h"
+#include "td_terms.hpp"
 #include "xa_adam.hpp"
 #include "xa_common.hpp"
 
 namespace {
 
+using xa_td::act_grad;
 typedef __attribute__((address_space(1))) unsigned gu32;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
@@ -104,15 +106,6 @@ XA_DEV float ldw(const float* p, bool coh) { return coh ? ldc(p) : ldg(p); }
 // one 16-B write-through store (a vector store)
 XA_DEV void st4c(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, f32x4v v) {
   __builtin_amdgcn_raw_buffer_store_b128(v, r, byte_off, 0, kAuxSc1);
-}
-
-XA_DEV float philox_normal(uint32_t i, uint32_t j, uint64_t ctr, uint64_t seed) {
-  // the same draw as xa_noisy_actions (offpolicy.hip)
-  const xa_u4 r = xa_philox(i, j, (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed,
-                            (uint32_t)(seed >> 32));
-  const float u1 = ((float)(r.x >> 8) + 1.0f) * 5.9604644775390625e-08f;
-  const float u2 = (float)(r.y >> 8) * 5.9604644775390625e-08f;
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
 // ---- network views ----
@@ -488,8 +481,8 @@ XA_DEV float4 dz_form4(const Lds& s, const DZ& d, float4 h, int rr, int kk) {
       g[u] = d.c3 * w[0];
     }
   }
-  return make_float4(h.x > 0.0f ? g[0] : 0.0f, h.y > 0.0f ? g[1] : 0.0f,
-                     h.z > 0.0f ? g[2] : 0.0f, h.w > 0.0f ? g[3] : 0.0f);
+  return make_float4(act_grad(g[0], h.x, XA_ACT_RELU), act_grad(g[1], h.y, XA_ACT_RELU),
+                     act_grad(g[2], h.z, XA_ACT_RELU), act_grad(g[3], h.w, XA_ACT_RELU));
 }
 XA_DEV float4 dz_form4(const Lds& s, const DZ& d, float4 h, int rr, int kk) {
   return d.n3 == 1 ? dz_form4<1>(s, d, h, rr, kk)
@@ -506,7 +499,7 @@ XA_DEV float dz_form(const Lds& s, const DZ& d, float h, int rr, int kk) {
   } else {
     g = d.c3 * s.aux[kk * d.n3];
   }
-  return h > 0.0f ? g : 0.0f;
+  return act_grad(g, h, XA_ACT_RELU);
 }
 
 // ---- the tile product: wave w, rows 16 w .. 16 w + 15, 16 columns; K padded to 16 ----
@@ -551,14 +544,6 @@ XA_DEV f32x4v tile_mma(const Lds& s, int Kp) {
 // ---- epilogue helpers: lane l holds D[4 (l >> 4) + r][l & 15] of the wave's 16 rows ----
 XA_DEV int out_row(int r) { return 16 * (threadIdx.x >> 6) + 4 * ((threadIdx.x & 63) >> 4) + r; }
 XA_DEV int out_col() { return threadIdx.x & 15; }
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
-
-XA_DEV float act_f(float v, int act) {
-  if (act == ACT_RELU) return fmaxf(v, 0.0f);
-  if (act == ACT_TANH) return xa_tanhf(v);
-  return v;
-}
 
 // ---- narrow follow-on products (the L3 heads, d pi) as column-tile partials: a forward /
 // input-gradient job also sums its 16 columns' share of out[r][n] = sum_c y[r][c] Wh(c, n)
@@ -743,8 +728,8 @@ __device__ __noinline__ bool fwd_tile(const int64_t* slots) {
   float4 y = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (st) {
     const float4 z = tile_out4();
-    y = make_float4(act_f(z.x + bv.x, act), act_f(z.y + bv.y, act), act_f(z.z + bv.z, act),
-                    act_f(z.w + bv.w, act));
+    y = make_float4(xa_td::act(z.x + bv.x, act), xa_td::act(z.y + bv.y, act),
+                    xa_td::act(z.z + bv.z, act), xa_td::act(z.w + bv.w, act));
     st4c(rsrc(out), (uint32_t)(((int64_t)row * N + c) * 4), f32x4v{y.x, y.y, y.z, y.w});
   }
   return head_partial(h, wv, y, row, B);
@@ -822,8 +807,8 @@ __device__ __noinline__ bool dx_tile_lds() {
   float4 y = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (st) {
     const float4 z = tile_out4();
-    y = make_float4(gv.x > 0.0f ? z.x : 0.0f, gv.y > 0.0f ? z.y : 0.0f,
-                    gv.z > 0.0f ? z.z : 0.0f, gv.w > 0.0f ? z.w : 0.0f);
+    y = make_float4(act_grad(z.x, gv.x, XA_ACT_RELU), act_grad(z.y, gv.y, XA_ACT_RELU),
+                    act_grad(z.z, gv.z, XA_ACT_RELU), act_grad(z.w, gv.w, XA_ACT_RELU));
     st4c(rsrc(out), (uint32_t)(((int64_t)row * ld + c) * 4), f32x4v{y.x, y.y, y.z, y.w});
   }
   return head_partial(h, wv, y, row, B);
@@ -963,7 +948,7 @@ XA_DEV void adam_one(const Net& n, float g, int i, float omb1, float omb2, float
   stg(n.v + i, v);
   if (target) {
     const float y = ldg(target + i);
-    stg(target + i, tau == 1.0f ? th : (1.0f - tau) * y + tau * th);
+    stg(target + i, xa_td::polyak(y, th, tau));
   }
 }
 
@@ -1005,7 +990,7 @@ __device__ __noinline__ void adam_range(Net n, const float* grad, int lo, int hi
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         adam_elem(gp[c] * gs, tp[c], mp[c], vp[c], n.alpha, omb1, omb2, eps);
-        yp[c] = tau == 1.0f ? tp[c] : (1.0f - tau) * yp[c] + tau * tp[c];
+        yp[c] = xa_td::polyak(yp[c], tp[c], tau);
       }
       st4c(rt, (uint32_t)i * 4u, f32x4v{th[u].x, th[u].y, th[u].z, th[u].w});
       stg4(n.m + i, m[u]);
@@ -1095,7 +1080,7 @@ XA_DEV void dw_job(const XSrc& x, const int64_t* slots, const DZ& d, int nin, in
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         adam_elem(gp[c], tp[c], mp[c], vp[c], an.alpha, omb1, omb2, eps);
-        yp[c] = tau == 1.0f ? tp[c] : (1.0f - tau) * yp[c] + tau * tp[c];
+        yp[c] = xa_td::polyak(yp[c], tp[c], tau);
       }
       st4c(rt, (uint32_t)eq[u] * 4u, f32x4v{thq[u].x, thq[u].y, thq[u].z, thq[u].w});
       stg4(an.m + eq[u], mq[u]);
@@ -1110,7 +1095,7 @@ XA_DEV void dw_job(const XSrc& x, const int64_t* slots, const DZ& d, int nin, in
         stc(an.th + eb, bth);
         stg(an.m + eb, bm);
         stg(an.v + eb, bv);
-        if (target) stg(target + eb, tau == 1.0f ? bth : (1.0f - tau) * btg + tau * bth);
+        if (target) stg(target + eb, xa_td::polyak(btg, bth, tau));
       }
     }
   } else if (ao.on) {
@@ -1147,7 +1132,7 @@ XA_DEV void dw_job(const XSrc& x, const int64_t* slots, const DZ& d, int nin, in
       stc(an.th + e, th_);
       an.m[e] = m_;
       an.v[e] = v_;
-      if (target) target[e] = tau == 1.0f ? th_ : (1.0f - tau) * tg_ + tau * th_;
+      if (target) target[e] = xa_td::polyak(tg_, th_, tau);
     };
 #pragma unroll
     for (int t = 0; t < kMaxDwTiles; ++t)
@@ -1553,7 +1538,7 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
       const Net n = net_of(id);
       if (layer == 1) {
         fwd_job(in_of(id), slots, rt * kTR, B, n.th + n.w1, n.th + n.b1, n.in, H1, ct * kCols,
-                ACT_RELU, ws.h1(id));
+                XA_ACT_RELU, ws.h1(id));
       } else {
         // + the L3 partials of the tile's 16 units; the row tile's last job finishes L3:
         // target actor tanh (+ TD3 smoothing noise, clip) -> a', critics -> v1, v2,
@@ -1561,7 +1546,7 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
         const Head hd{n.th + n.w3, ws.hp3(id), ws.ticket(id, rt), n.out, 1, n.out, ct, CT2,
                       false};
         if (fwd_job(xsrc(ws.h1(id), H1, H1, false, true), slots, rt * kTR, B, n.th + n.w2,
-                    n.th + n.b2, H1, H2, ct * kCols, ACT_RELU, ws.h2(id), false, hd)) {
+                    n.th + n.b2, H1, H2, ct * kCols, XA_ACT_RELU, ws.h2(id), false, hd)) {
           const int N = n.out, r0 = rt * kTR, nr = min(kTR, B - r0);
           for (int e = tid; e < nr * N; e += 256) {
             const int row = r0 + e / N, c = e % N;
@@ -1569,11 +1554,8 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
             if (id == N_TA) {
               float a = xa_tanhf(z);
               if (p.smooth) {
-                float nz = 0.0f;
-                if (p.noise_sigma != 0.0f) {
-                  nz = philox_normal((uint32_t)row, (uint32_t)c, ctr, p.seed) * p.noise_sigma;
-                  nz = fminf(fmaxf(nz, -p.noise_clip), p.noise_clip);
-                }
+                const float nz = xa_td::clipped_noise((uint32_t)row, (uint32_t)c, ctr, p.seed,
+                                                      p.noise_sigma, p.noise_clip);
                 if (p.noise_out) p.noise_out[row * A + c] = nz;
                 a = fminf(fmaxf(a + nz, -1.0f), 1.0f);
               }
@@ -1592,8 +1574,7 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
   }
 
   // ---- P4 / P5: target critics L1 on [s', a'], L2 (+ the target values' partials; the
-  // row tile's last job runs the TD head: y = r + (1 - d) gamma min(tv1, tv2),
-  // dv = 2 (v - y) (MSE) or clip(v - y, +-delta) (opt-in Huber), per-sample loss) ----
+  // row tile's last job runs the TD head: xa_critic_td_grad's arithmetic, td_terms.hpp) ----
   for (int layer = 1; layer <= 2; ++layer) {
     const int CT = layer == 1 ? CT1 : CT2, per = RTT * CT;
     for (int j = b; j < nt * per; j += G) {
@@ -1602,12 +1583,13 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
       const Net n = net_of(id);
       if (layer == 1) {
         fwd_job(xcat(xsrc(p.out_s2, S, S, false, true), ws.ta, A, A, false, true), slots,
-                rt * kTR, B, n.th + n.w1, n.th + n.b1, C, H1, ct * kCols, ACT_RELU, ws.h1(id));
+                rt * kTR, B, n.th + n.w1, n.th + n.b1, C, H1, ct * kCols, XA_ACT_RELU,
+                ws.h1(id));
       } else {
         const Head hd{n.th + n.w3, ws.hp3(id), ws.ticket(N_TC1, rt), 1, 1, 1, ct, nt * CT2,
                       false};
         if (fwd_job(xsrc(ws.h1(id), H1, H1, false, true), slots, rt * kTR, B, n.th + n.w2,
-                    n.th + n.b2, H1, H2, ct * kCols, ACT_RELU, ws.h2(id), false, hd)) {
+                    n.th + n.b2, H1, H2, ct * kCols, XA_ACT_RELU, ws.h2(id), false, hd)) {
           const int r0 = rt * kTR, nr = min(kTR, B - r0);
           if (tid < nr) {
             const int row = r0 + tid;
@@ -1616,23 +1598,15 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
                 ? fminf(t1, head_total(ws.hp3(N_TC2), CT2, B, 1, row, 0) + tc2.th[tc2.b3])
                 : t1;
             const int64_t sl = td3_slots[row];
-            const float yv = p.ring_rewards[sl] + ((1.0f - p.ring_dones[sl]) * p.gamma) * tv;
+            const float yv =
+                xa_td::critic_target(p.ring_rewards[sl], p.ring_dones[sl], p.gamma, tv);
             const float hdl = p.huber_delta;
-            auto term = [hdl](float e, float& d) {
-              if (hdl > 0.0f) {
-                d = fminf(fmaxf(e, -hdl), hdl);
-                const float ae = fabsf(e);
-                return ae <= hdl ? 0.5f * (e * e) : hdl * (ae - 0.5f * hdl);
-              }
-              d = 2.0f * e;
-              return e * e;
-            };
             float d1;
-            float l = term(ldc(ws.v1 + row) - yv, d1);
+            float l = xa_td::td_term(ldc(ws.v1 + row) - yv, hdl, d1);
             stc(p.dv1 + row, d1);
             if (twin) {
               float d2;
-              l = l + term(ldc(ws.v2 + row) - yv, d2);
+              l = l + xa_td::td_term(ldc(ws.v2 + row) - yv, hdl, d2);
               stc(p.dv2 + row, d2);
             }
             if (p.loss_out) p.loss_out[row] = l;
@@ -1738,10 +1712,10 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
         const int rt = j / CT, ct = j % CT;
         if (layer == 1)
           fwd_job(spa, slots, rt * kTR, B, c1.th + c1.w1, c1.th + c1.b1, C, H1, ct * kCols,
-                  ACT_RELU, ws.q1, true);
+                  XA_ACT_RELU, ws.q1, true);
         else
           fwd_job(xsrc(ws.q1, H1, H1, false, true), slots, rt * kTR, B, c1.th + c1.w2,
-                  c1.th + c1.b2, H1, H2, ct * kCols, ACT_RELU, ws.q2, true);
+                  c1.th + c1.b2, H1, H2, ct * kCols, XA_ACT_RELU, ws.q2, true);
         __syncthreads();
       }
       if (!grid_sync(y, s_flag, RTT * CT, layer == 1 ? pre_p10() : pre_p11())) return;
@@ -1762,7 +1736,7 @@ __global__ __launch_bounds__(256) void td3_update_kernel(XaTd3UpdateArgs p) {
           const int row = r0 + e / A, c = e % A;
           const float dp = head_total(ws.hpp, CT1, B, A, row, c);
           const float pv = ldc(ws.pa + row * A + c);
-          stc(ws.dz3 + row * A + c, dp * (1.0f - pv * pv));
+          stc(ws.dz3 + row * A + c, act_grad(dp, pv, XA_ACT_TANH));
         }
       }
       __syncthreads();
@@ -1888,7 +1862,7 @@ __global__ __launch_bounds__(256) void td3_act_kernel(XaTd3ActArgs p) {
   for (int j = b; j < RTT * CT1; j += G) {
     const int rt = j / CT1, ct = j % CT1;
     fwd_job(xsrc(p.states, S, S, false, false), nullptr, rt * kTR, n, ac.th + ac.w1,
-            ac.th + ac.b1, S, H1, ct * kCols, ACT_RELU, ws.h1(N_AC));
+            ac.th + ac.b1, S, H1, ct * kCols, XA_ACT_RELU, ws.h1(N_AC));
     __syncthreads();
   }
   auto pre_act2 = [&]() {
@@ -1901,16 +1875,13 @@ __global__ __launch_bounds__(256) void td3_act_kernel(XaTd3ActArgs p) {
     const int rt = j / CT2, ct = j % CT2;
     const Head hd{ac.th + ac.w3, ws.hp3(N_AC), ws.ticket(N_AC, rt), A, 1, A, ct, CT2, false};
     if (fwd_job(xsrc(ws.h1(N_AC), H1, H1, false, true), nullptr, rt * kTR, n, ac.th + ac.w2,
-                ac.th + ac.b2, H1, H2, ct * kCols, ACT_RELU, ws.h2(N_AC), false, hd)) {
+                ac.th + ac.b2, H1, H2, ct * kCols, XA_ACT_RELU, ws.h2(N_AC), false, hd)) {
       const int r0 = rt * kTR, nr = min(kTR, n - r0);
       for (int e = tid; e < nr * A; e += 256) {
         const int row = r0 + e / A, c = e % A;
         const float z = head_total(ws.hp3(N_AC), CT2, n, A, row, c) + ac.th[ac.b3 + c];
-        float nz = 0.0f;
-        if (p.sigma != 0.0f) {
-          nz = philox_normal((uint32_t)row, (uint32_t)c, ctr, p.seed) * p.sigma;
-          nz = fminf(fmaxf(nz, -p.noise_clip), p.noise_clip);
-        }
+        const float nz = xa_td::clipped_noise((uint32_t)row, (uint32_t)c, ctr, p.seed, p.sigma,
+                                              p.noise_clip);
         if (p.noise_out) p.noise_out[row * A + c] = nz;
         p.out[(int64_t)row * p.ld_out + c] = fminf(fmaxf(xa_tanhf(z) + nz, p.lo), p.hi);
       }
