@@ -908,6 +908,47 @@ int xa_critic_td_grad(const float* v1, const float* v2, const float* tv1, const 
                       const float* rewards, const float* dones, int batch, float gamma,
                       float huber_delta, float* dv1, float* dv2, float* loss, void* stream);
 
+/* Soft Actor-Critic (https://arxiv.org/abs/1812.05905; csrc/sac_terms.hpp states the
+ * arithmetic). alpha = exp(*log_alpha) is read on device by every launch that uses it.
+ *
+ * Tanh-squashed Gaussian head over n rows of act_dim elements: ls = clamp(log_std, -20, 2),
+ * u = mean + exp(ls) eps, actions = tanh(u), logp[row] = sum_j (-0.5 eps^2 - ls -
+ * 0.5 log(2 pi) - log(1 - tanh(u)^2)) in index order (the last term in its overflow-free
+ * softplus form, no additive epsilon). eps: eps_in [n][act_dim] when given, else Philox
+ * normals at (row, j, *rng_counter), key seed (xa_noisy_actions' draw); deterministic: eps = 0
+ * (actions = tanh(mean)), nothing drawn. mean / log_std / actions carry leading dimensions
+ * (actions may be the action columns of an [s, a] buffer); eps_out [n][act_dim] and logp [n]
+ * are optional. */
+int xa_sac_sample(const float* mean, int64_t ld_mean, const float* log_std, int64_t ld_log_std,
+                  int n, int act_dim, const float* eps_in, const uint64_t* rng_counter,
+                  uint64_t seed, int deterministic, float* actions, int64_t ld_actions,
+                  float* eps_out, float* logp, void* stream);
+
+/* xa_critic_td_grad for SAC's twin critics: y = r + ((1 - d) gamma) (min(tv1, tv2) -
+ * alpha logp_next); dv_i and loss[b] (optional) as there (huber_delta > 0: Huber-TD). */
+int xa_sac_td_grad(const float* v1, const float* v2, const float* tv1, const float* tv2,
+                   const float* logp_next, const float* log_alpha, const float* rewards,
+                   const float* dones, int batch, float gamma, float huber_delta, float* dv1,
+                   float* dv2, float* loss, void* stream);
+
+/* Actor loss rows loss[b] = alpha logp - min(q1, q2) (optional) and the seeds of the critics'
+ * input-gradient passes, d(-mean Qmin)/dq: -1 / batch on the critic holding the minimum (ties:
+ * critic 1), 0 on the other. dlog_alpha[0] (optional) = -mean(logp + target_entropy), the
+ * temperature gradient: one workgroup sums it in a fixed order that depends on batch only. */
+int xa_sac_actor_seed(const float* q1, const float* q2, const float* logp,
+                      const float* log_alpha, int batch, float target_entropy, float* dq1,
+                      float* dq2, float* loss, float* dlog_alpha, void* stream);
+
+/* Reparameterised head gradient from da = d(-mean Qmin)/d action (the summed critic input
+ * gradients' action columns, leading dimension ld_da), the sampled actions, their eps and
+ * the actor's log_std: du = da (1 - a^2) + (alpha / batch) 2 a; dmean = du; dlog_std =
+ * clampgrad (du exp(ls) eps - alpha / batch), clampgrad 0 where log_std lies strictly outside
+ * [-20, 2]. dmean / dlog_std [batch][act_dim]. */
+int xa_sac_head_grad(const float* da, int64_t ld_da, const float* actions, int64_t ld_actions,
+                     const float* eps, const float* log_std, int64_t ld_log_std,
+                     const float* log_alpha, int batch, int act_dim, float* dmean,
+                     float* dlog_std, void* stream);
+
 /* One network of the fused TD3 / DDPG gradient step: the flat Keras-order parameters of a
  * 3-layer .cfg MLP (W1 [in][h1], b1, W2 [h1][h2], b2, W3 [h2][out], b3) and, for the
  * networks that learn, their Keras Adam state (t = *step + 1 this step; the launch adds 1). */

@@ -3,13 +3,14 @@
 Agent registry and command table mirror xagents/__init__.py:18-40. Only the
 agents whose hot path is built are registered (see DESIGN.md for scope).
 """
-from xagents_amd import a2c, acer, ddpg, dqn, ppo, td3, trpo
+from xagents_amd import a2c, acer, ddpg, dqn, ppo, sac, td3, trpo
 from xagents_amd.a2c.agent import A2C
 from xagents_amd.acer.agent import ACER
 from xagents_amd.base import BaseAgent, OffPolicy, OnPolicy
 from xagents_amd.ddpg.agent import DDPG
 from xagents_amd.dqn.agent import DQN
 from xagents_amd.ppo.agent import PPO
+from xagents_amd.sac.agent import SAC
 from xagents_amd.td3.agent import TD3
 from xagents_amd.trpo.agent import TRPO
 from xagents_amd.utils.common import register_models
@@ -23,8 +24,9 @@ agents = {
     'dqn': {'module': dqn, 'agent': DQN},
     'ddpg': {'module': ddpg, 'agent': DDPG},
     'td3': {'module': td3, 'agent': TD3},
+    'sac': {'module': sac, 'agent': SAC},
     'trpo': {'module': trpo, 'agent': TRPO},
 }
 register_models(agents)
 
-__all__ = ['A2C', 'ACER', 'DDPG', 'DQN', 'PPO', 'TD3', 'TRPO', 'BaseAgent', 'OnPolicy', 'OffPolicy', 'agents']
+__all__ = ['A2C', 'ACER', 'DDPG', 'DQN', 'PPO', 'SAC', 'TD3', 'TRPO', 'BaseAgent', 'OnPolicy', 'OffPolicy', 'agents']

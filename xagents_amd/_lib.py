@@ -553,6 +553,26 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
          c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    'xa_sac_sample': (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_uint64, c_int,
+         c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    'xa_sac_td_grad': (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    'xa_sac_actor_seed': (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    'xa_sac_head_grad': (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+         c_int, c_void_p, c_void_p, c_void_p],
+    ),
     'xa_activation_grad': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'xa_peer_block_bytes': (ctypes.c_size_t, [ctypes.c_size_t, c_int]),
     'xa_peer_state_words': (c_int, [ctypes.c_size_t]),

@@ -474,11 +474,12 @@ class LayerExecutor:
 
     # ---- backward ----------------------------------------------------------------
     def backward(self, d_outputs, grad, batch=None, dinput=None, accumulate=False,
-                 on_grad=None, adam=None):
+                 on_grad=None, adam=None, dinput_accumulate=False):
         """d_outputs: gradients w.r.t. the output layers (model.outputs order, [b, n]).
         Writes the flat parameter gradient into `grad` (Keras variable order; None skips
         the parameter gradients) and, if given, d(loss)/d(input) into `dinput` [b, in]
-        (dense input layers). `batch` (<= B) back-propagates only the first rows of the
+        (dense input layers; `dinput_accumulate` adds to it: the sum of two networks' input
+        gradients). `batch` (<= B) back-propagates only the first rows of the
         last forward (samples are independent rows, so a prefix of every buffer is a
         smaller batch). `accumulate` adds the parameter gradient to `grad` (chunked
         minibatches). `on_grad(w0)` is called once the launches writing a layer's weight
@@ -600,7 +601,7 @@ class LayerExecutor:
                 if j == -1 and dinput is not None:
                     gemm(Bb, n_in, n_out, d.data_ptr(), tp + 4 * w0, dinput.data_ptr(),
                          a_m=(1, n_out, 0), b_ks=1, b_ns=n_out, ldc=n_in,
-                         workspace=self.workspace)
+                         beta=dinput_accumulate, workspace=self.workspace)
                 if j != -1:
                     # dX = dZ W^T (gated by the source layer's ReLU), accumulated over heads
                     ev = self._timing_start()

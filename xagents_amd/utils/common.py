@@ -109,8 +109,8 @@ def register_models(agents):
 def create_model(env, agent_id, model_type, optimizer_kwargs=None, seed=None, model_cfg=None,
                  device=None):
     """Output-unit rules of xagents/utils/common.py:447-487: [n_actions] (+[1] for
-    actor-critic cfgs, acer duplicates, critics output 1; td3/ddpg critics take
-    obs + action inputs)."""
+    actor-critic cfgs, acer duplicates, critics output 1; td3/ddpg/sac critics take
+    obs + action inputs; the sac actor emits [mean, log_std], n_actions each)."""
     import xagents_amd
     from xagents_amd.envs import Box, Discrete
     from xagents_amd.nets import Adam, ModelReader
@@ -134,8 +134,10 @@ def create_model(env, agent_id, model_type, optimizer_kwargs=None, seed=None, mo
         units.append(1)
     elif 'critic' in name:
         units[0] = 1
+    elif agent_id == 'sac':
+        units.append(units[-1])
     input_shape = env.observation_space.shape
-    if agent_id in ('td3', 'ddpg') and 'critic' in name:
+    if agent_id in ('td3', 'ddpg', 'sac') and 'critic' in name:
         assert isinstance(space, Box), (
             f'Invalid environment: {env.spec.id}. {agent_id.upper()} supports '
             f'environments with a Box action space only, got {space}'
@@ -166,7 +168,7 @@ def create_buffers(agent_id, max_size, batch_size, n_envs, initial_size=None, as
     if agent_id == 'acer':
         batch_size = 1
     kwargs = dict(initial_size=initial_size, batch_size=batch_size)
-    if agent_id in ('td3', 'ddpg'):
+    if agent_id in ('td3', 'ddpg', 'sac'):
         return [ReplayBuffer2(max_size, 5, **kwargs) for _ in range(n_envs)]
     return [ReplayBuffer1(max_size, **kwargs) for _ in range(n_envs)]
 
@@ -201,6 +203,11 @@ def create_agent(agent_id, agent_kwargs, non_agent_kwargs, trial=None):
     if weights:
         n_models = len(agent.output_models)
         assert len(weights) == n_models, f'Expected {n_models} weights to load, got {len(weights)}'
+        if hasattr(agent, 'load_weights'):
+            # the agent's checkpoints carry more than its output models (SAC: the target
+            # critics and the temperature)
+            agent.load_weights(weights)
+            return agent
         for weight, model in zip(weights, agent.output_models):
             model.load_weights(weight).expect_partial()
     return agent
