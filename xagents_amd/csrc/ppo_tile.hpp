@@ -33,6 +33,8 @@
 // consecutive (coalesced) accesses, and a wave stores a dW2 accumulator tile as 16 runs of
 // 256 contiguous bytes; non-W2 value number rr sits at x = H*H + rr.
 #pragma once
+#include <type_traits>
+
 #include "ac_tile.hpp"
 
 namespace xa_pt {
@@ -207,21 +209,37 @@ XA_DEV float2 xa_swap32(float v) {
   return make_float2(__uint_as_float(a[0]), __uint_as_float(a[1]));
 }
 
+// The thread index a caller wants the lane predicates formed from (pt_tile,
+// pt_write_row_rest): by default the lane's own index values, the very ones the addresses
+// use. The headline update kernel passes a per-step opaque copy of threadIdx.x instead (an
+// int), so each predicate is a compare at its use and not a mask kept across the step loop.
+struct PtOwnTid {};
+template <class PTid>
+XA_DEV void pt_pred_lane(PTid ptid, int& pw, int& pli, int& plq) {
+  if constexpr (!std::is_same<PTid, PtOwnTid>::value) {
+    pw = ptid >> 6;
+    pli = ptid & 15;
+    plq = (ptid & 63) >> 4;
+  }
+}
+
 // One tile: rec = TS packed LDS records {obs[OBS], action (< 0: padding), return, old
 // value, old log-prob}; w2c = the thread's W2 column slice, w2r = load_w2_rows (with
 // kRegH1 loaded here, after the first barrier); w1v / b1v = the lane's own layer-1 weight
 // W1[lq][i] and (row 0) b1[i] (kRegH1; unused otherwise); on the block's last tile of the
 // step (last) w2_out(acc) runs right after the dW2 MFMAs. Ends after the dW1 accumulation
 // (no trailing barrier; the next tile's first LDS writes come after the other waves passed
-// this tile's last barrier).
-template <int OBS, int A, int TS, class Stamp, class W2Out>
+// this tile's last barrier). ptid: see PtOwnTid.
+template <int OBS, int A, int TS, class Stamp, class W2Out, class PTid = PtOwnTid>
 XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg,
                     const float* rec, const float (&w2c)[16], float (&w2r)[16], float w1v,
-                    float b1v, Stamp stamp, bool last, W2Out w2_out) {
+                    float b1v, Stamp stamp, bool last, W2Out w2_out, PTid ptid = PTid()) {
   static_assert(TS == 16 || TS == 32, "tile sizes: 16 or 32 samples");
   constexpr int NT = TS / 16, AH = A + 1, R = OBS + 4, LDT = PtLds<OBS, A, TS>::LDT;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int li = lane & 15, lq = lane >> 4;
+  int pw = w, pli = li, plq = lq;  // the same, for predicates
+  pt_pred_lane(ptid, pw, pli, plq);
   const int i = 16 * w + li;  // this lane's hidden unit
   // ---- 1: H1 ----
   float h1[NT][4];
@@ -234,11 +252,11 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
       const float2 s16 = xa_swap16(w1v), s32 = xa_swap32(w1v);
       float vj[4];                        // vj[j] = W1[lq ^ j][i]
       vj[0] = w1v;
-      vj[1] = (lq & 1) ? s16.x : s16.y;  // row lq ^ 1
+      vj[1] = (plq & 1) ? s16.x : s16.y;  // row lq ^ 1
       const float2 s48 = xa_swap32(vj[1]);
-      vj[2] = (lq & 2) ? s32.x : s32.y;  // row lq ^ 2
-      vj[3] = (lq & 2) ? s48.x : s48.y;  // row lq ^ 3
-      const bool o1 = lq & 1, o2 = lq & 2;
+      vj[2] = (plq & 2) ? s32.x : s32.y;  // row lq ^ 2
+      vj[3] = (plq & 2) ? s48.x : s48.y;  // row lq ^ 3
+      const bool o1 = plq & 1, o2 = plq & 2;
 #pragma unroll
       for (int k = 0; k < OBS; ++k) {  // j = k ^ lq
         const float e0 = ((k & 1) != 0) != o1 ? vj[1] : vj[0];
@@ -314,7 +332,7 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
 #pragma unroll
       for (int a = 0; a < AH; ++a) {
         const float p = xa_sum16(h2[mt][r] * w34[a]);
-        if (li == 0) L.sZp[w][16 * mt + 4 * lq + r][a] = p;
+        if (pli == 0) L.sZp[w][16 * mt + 4 * lq + r][a] = p;
       }
   __syncthreads();
   stamp(52);
@@ -322,7 +340,7 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
   // lq repeat it), handed to the lanes that need it through a wave-private LDS copy; dA2,
   // head grads, dW2 ----
   constexpr int AHP = PtLds<OBS, A, TS>::AHP;
-  const bool tally = w == 0 && lq == 0;  // one lane per sample accumulates the sums
+  const bool tally = pw == 0 && plq == 0;  // one lane per sample accumulates the sums
 #pragma unroll
   for (int mt = 0; mt < NT; ++mt) {
     const int s = 16 * mt + li;
@@ -385,7 +403,7 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
         for (int a = 0; a < AH; ++a) acc.gb34[a] += dz[a];
       }
     }
-    if (lq == 0) {
+    if (plq == 0) {
 #pragma unroll
       for (int a4 = 0; a4 < AHP; a4 += 4)
         *reinterpret_cast<float4*>(&L.sdz[w][s][a4]) = make_float4(dz[a4], dz[a4 + 1], dz[a4 + 2], dz[a4 + 3]);
@@ -486,13 +504,16 @@ XA_DEV void pt_write_row_w2(const PtAcc<OBS, A>& acc, PutPair put_pair) {
 }
 
 // the rest of the row (pt_write_row without its W2 part, which pt_tile stored early)
-template <int OBS, int A, class Put>
-XA_DEV void pt_write_row_rest(PtAcc<OBS, A>& acc, Put put, bool loss_sums = true) {
+template <int OBS, int A, class Put, class PTid = PtOwnTid>
+XA_DEV void pt_write_row_rest(PtAcc<OBS, A>& acc, Put put, bool loss_sums = true,
+                              PTid ptid = PTid()) {
   constexpr int AH = A + 1;
   const Offs o = offs(OBS, A);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int li = lane & 15, lq = lane >> 4;
   const int i = 16 * w + li;
+  int pw = w, pli = li, plq = lq;  // the same, for predicates
+  pt_pred_lane(ptid, pw, pli, plq);
   // sum over the lane groups lq in the fixed order (lq0 + lq1) + (lq2 + lq3), every lane:
   // v_permlane16_swap / v_permlane32_swap exchange rows 0 <-> 1, 2 <-> 3 and halves
   auto red = [](float v) {
@@ -507,7 +528,7 @@ XA_DEV void pt_write_row_rest(PtAcc<OBS, A>& acc, Put put, bool loss_sums = true
   for (int k = 0; k < OBS; ++k) acc.gW1[k] = red(acc.gW1[k]);
   acc.gb1 = red(acc.gb1);
   acc.gb2 = red(acc.gb2);
-  if (w == 0) {  // the tally lanes: wave 0, lq == 0, one sample each
+  if (pw == 0) {  // the tally lanes: wave 0, lq == 0, one sample each
 #pragma unroll
     for (int a = 0; a < AH; ++a) acc.gb34[a] = xa_sum16(acc.gb34[a]);
     if (loss_sums) {  // (wave 0 is the last to reach the row barrier: skipped when unused)
@@ -517,7 +538,7 @@ XA_DEV void pt_write_row_rest(PtAcc<OBS, A>& acc, Put put, bool loss_sums = true
       acc.l_cnt = xa_sum16(acc.l_cnt);
     }
   }
-  if (lq == 0) {
+  if (plq == 0) {
 #pragma unroll
     for (int a = 0; a < A; ++a) put(exchange_of_rest<OBS, A>(o.w3 + i * A + a), acc.gW34[a]);
     put(exchange_of_rest<OBS, A>(o.w4 + i), acc.gW34[A]);
@@ -525,7 +546,7 @@ XA_DEV void pt_write_row_rest(PtAcc<OBS, A>& acc, Put put, bool loss_sums = true
     put(exchange_of_rest<OBS, A>(o.b1 + i), acc.gb1);
 #pragma unroll
     for (int k = 0; k < OBS; ++k) put(exchange_of_rest<OBS, A>(o.w1 + k * H + i), acc.gW1[k]);
-    if (w == 0 && li == 0) {
+    if (pw == 0 && pli == 0) {
 #pragma unroll
       for (int a = 0; a < A; ++a) put(exchange_of_rest<OBS, A>(o.b3 + a), acc.gb34[a]);
       put(exchange_of_rest<OBS, A>(o.b4), acc.gb34[A]);

@@ -600,6 +600,47 @@ struct UpdLds {
 // write-through. Placement decides speed, never correctness.
 constexpr int kLocForceWt = 2;  // the kernel's loc argument: 0 spread, 1 XCD-local, 2 forced
 
+// The headline kernel's step loop (kUni* in the kernel): values it keeps in vector registers
+// or forms anew at their use, not as scalars and lane masks spilled across the loop.
+// Selected by a template flag so that a kernel without them holds no trace of them -- not
+// even an unused local, which has re-allocated other kernels' registers before.
+struct UniF {  // the optimizer's launch-uniform floats, each through a v_mov into a VGPR
+  float b1, b2, eps, clip, omb1, omb2;
+};
+struct NoUniF {  // (never read: XA_UF picks the kernel argument)
+  static constexpr float b1 = 0.0f, b2 = 0.0f, eps = 0.0f, clip = 0.0f, omb1 = 0.0f, omb2 = 0.0f;
+};
+XA_DEV float uni_vreg(float x) {
+  float r;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(x));
+  return r;
+}
+// tf.clip_by_global_norm's scale (phase C) from the VGPR-held clip norm: the opaque copy
+// keeps the `clip > 0` compare at its use (the compiler would hoist it out of the step loop
+// as one more spilled mask)
+XA_DEV float uni_clip_scale(float clip, float gn) {
+  asm volatile("" : "+v"(clip));
+  return clip > 0.0f ? clip * fminf(frcp(gn), frcp(clip)) : 1.0f;
+}
+// the thread index for a lane predicate: an opaque copy per use (no instruction; the
+// compiler can no longer tell that the predicate is the same in every step), or the index
+template <bool ON>
+XA_DEV int uni_tid(int tid) {
+  if constexpr (ON) asm volatile("" : "+v"(tid));
+  return tid;
+}
+// the same for the tile's predicates (ppo_tile.hpp: PtOwnTid = its own index values)
+template <bool ON>
+XA_DEV auto uni_ptid(int tid) {
+  if constexpr (ON) {
+    asm volatile("" : "+v"(tid));
+    return tid;
+  } else {
+    return PtOwnTid{};
+  }
+}
+
+
 // TS = samples per tile (32; 16 when the minibatch has at most 16 tiles of 32: twice the
 // blocks, half the element-wise work per block and step); PRE = every tile input of the
 // launch fits the block's LDS records (gathered once in phase 0); loc = XCD-local mode
@@ -1107,6 +1148,41 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     return bad;
   };
 
+  // The headline kernel's step loop runs one wave per SIMD and is short of scalar registers,
+  // not of vector ones: what it would keep as loop-invariant scalars and lane masks it spills
+  // to VGPR lanes and reads back every step. So there (kUni*; each an A/B switch):
+  //   kUniP  the lane predicates are formed from an opaque copy of the thread index
+  //          (uni_tid / uni_ptid, and per step the slice's slot indices): a compare at each
+  //          use and no mask kept
+  //   kUniF  the uniform floats of the loss and the optimizer sit in vector registers
+  //   kUniB  the block index is told to lie inside the fixed grid (the host launches exactly
+  //          FixShape::G logical blocks of this kernel): "this block has no tile of the
+  //          minibatch" is then false at compile time, and the zero-row stores behind it
+  //          (never run at this shape) leave the loop
+  // Outputs are bit for bit what they were; every other kernel compiles to the same code
+  // (profiles/ppo_update_scalar_reloads.txt, ppo_update_scalar_reloads_ab.txt).
+#ifndef XA_UNI_PRED
+#define XA_UNI_PRED 1
+#endif
+#ifndef XA_UNI_FLOATS
+#define XA_UNI_FLOATS 1
+#endif
+#ifndef XA_UNI_BLOCK
+#define XA_UNI_BLOCK 1
+#endif
+  constexpr bool kUni = BF == 3 && !DP && OBS == 4 && A == 2;
+  constexpr bool kUniP = kUni && XA_UNI_PRED, kUniF = kUni && XA_UNI_FLOATS;
+  if constexpr (kUni && XA_UNI_BLOCK) __builtin_assume(b >= 0 && b < FS::G);
+  [[maybe_unused]] std::conditional_t<kUniF, UniF, NoUniF> uf;
+  if constexpr (kUniF) {
+    cfg.clip_norm = uni_vreg(cfg.clip_norm);
+    cfg.value_coef = uni_vreg(cfg.value_coef);
+    cfg.entropy_coef = uni_vreg(cfg.entropy_coef);
+    cfg.adv_eps = uni_vreg(cfg.adv_eps);
+    uf.b1 = uni_vreg(p.adam.beta1), uf.b2 = uni_vreg(p.adam.beta2), uf.eps = uni_vreg(p.adam.eps);
+    uf.clip = uni_vreg(p.adam.clip_norm), uf.omb1 = uni_vreg(omb1), uf.omb2 = uni_vreg(omb2);
+  }
+#define XA_UF(held, arg) (kUniF ? (held) : (arg))
   PtAcc<OBS, A> acc;
   float w2r[16];  // dH1's B operand: W2 row 16 w + li, columns 16 lq .. (load_w2_rows)
   int k_tr = 0;  // the step the tile trace points belong to
@@ -1143,6 +1219,10 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     if (form != form_sel) continue;
     if (kForms > 1 && form != 0) kWt = form == 1;  // (the value it has: a constant in this copy)
     for (int k = 0; k < K; ++k) {
+      if constexpr (kUniP) {
+#pragma unroll
+        for (int q = 0; q < RPT; ++q) asm volatile("" : "+v"(ps.rx[q]), "+v"(ps.rdst[q]));
+      }
       const int m = k % n_mb;
       const int cnt = min(MB, B - m * MB);
       const int n_tiles = (cnt + TS - 1) / TS;
@@ -1179,7 +1259,8 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
           XA_STAMP(35);
           const float* in = &U.pre[((size_t)k * TPB * TS + ((tile - b) / G) * TS) * (OBS + 4)];
 #ifndef XA_ABL_TILE  // diagnostic ablation builds (tools/ablate_update.py) only
-          pt_tile<OBS, A, TS>(L, acc, cfg, in, wv, w2r, rv[0], rv[1], stampf, last, w2_out);
+          pt_tile<OBS, A, TS>(L, acc, cfg, in, wv, w2r, rv[0], rv[1], stampf, last, w2_out,
+                              uni_ptid<kUniP>(tid));
 #else
           if (last) w2_out(acc);
 #endif
@@ -1219,7 +1300,8 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
           st_row1(rows_r, rows_o + (uint32_t)(((size_t)b * NP2 * 2 + P + tid) * 4), 0.0f, tag,
                   row_wt);
       } else {
-        pt_write_row_rest<OBS, A>(acc, [&](int x, float v) { srow[x] = v; }, XA_OUT(loss_out) != nullptr);
+        pt_write_row_rest<OBS, A>(acc, [&](int x, float v) { srow[x] = v; },
+                                  XA_OUT(loss_out) != nullptr, uni_ptid<kUniP>(tid));
       }
 #endif
       XA_STAMP(44);
@@ -1233,7 +1315,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       }
       if constexpr (!kRowDirect) {
         __syncthreads();
-        for (int c = H * H / 2 + tid; c < NP2; c += 256)
+        for (int c = H * H / 2 + uni_tid<kUniP>(tid); c < NP2; c += 256)
           st_row(rows_r, rows_o + (uint32_t)((size_t)b * NP2 + c) * kRowPB, srow[2 * c],
                  srow[2 * c + 1], tag, row_wt);
       } else if constexpr (BF == 0) {
@@ -1347,7 +1429,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       if (col_b) {
         double t0 = 0.0, t1 = 0.0;
         bool bad = false;
-        if (tid < parts_b * nc) {
+        if (uni_tid<kUniP>(tid) < parts_b * nc) {
           const int part = tid / nc, c = tid - part * nc;
           uint32_t off[kBF];
           RowG x[kBF];
@@ -1369,7 +1451,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
           U.red[(part * nc + c) * 2 + 1] = t1;
         }
         if (__syncthreads_or(bad)) return;
-        for (int c = tid; c < nc; c += 256) {
+        for (int c = uni_tid<kUniP>(tid); c < nc; c += 256) {
           double s0 = 0.0, s1 = 0.0;
           for (int part = 0; part < parts_b; ++part) {
             s0 += U.red[(part * nc + c) * 2];
@@ -1540,7 +1622,8 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
 #pragma unroll
       for (int q4 = 0; q4 < NQ4; ++q4) {
         const float4 a = U.mv4[0][q4][tid], c = U.mv4[1][q4][tid];
-        const xa_f2 b1 = {p.adam.beta1, p.adam.beta1}, b2 = {p.adam.beta2, p.adam.beta2};
+        const xa_f2 b1 = {XA_UF(uf.b1, p.adam.beta1), XA_UF(uf.b1, p.adam.beta1)};
+        const xa_f2 b2 = {XA_UF(uf.b2, p.adam.beta2), XA_UF(uf.b2, p.adam.beta2)};
         const xa_f2 m01 = xa_f2{a.x, a.y} * b1, m23 = xa_f2{a.z, a.w} * b1;
         const xa_f2 v01 = xa_f2{c.x, c.y} * b2, v23 = xa_f2{c.z, c.w} * b2;
         bm[4 * q4] = m01.x; bm[4 * q4 + 1] = m01.y; bm[4 * q4 + 2] = m23.x; bm[4 * q4 + 3] = m23.y;
@@ -1580,7 +1663,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
 #pragma unroll
         for (int q = 0; q < RPT; ++q) s0 = fma((double)gr[q], (double)gr[q], s0);
         const double ws = xa_wave_sum_f64(s0 + s1);
-        if (lane == 0) U.wsum[w] = ws;
+        if ((uni_tid<kUniP>(tid) & 63) == 0) U.wsum[w] = ws;
       }
       if (__syncthreads_or(bad)) return;
       XA_STAMP(47);
@@ -1590,8 +1673,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       // tf.clip_by_global_norm's scale clip * min(1 / norm, 1 / clip), on the hardware sqrt /
       // reciprocal units (the update is checked against float64 with a tolerance)
       const float gn = __builtin_amdgcn_sqrtf((float)tot);
-      const float sc = p.adam.clip_norm > 0.0f
-                           ? p.adam.clip_norm * fminf(frcp(gn), frcp(p.adam.clip_norm)) : 1.0f;
+      const float sc = XA_UF(uni_clip_scale(uf.clip, gn),
+                             p.adam.clip_norm > 0.0f
+                                 ? p.adam.clip_norm * fminf(frcp(gn), frcp(p.adam.clip_norm)) : 1.0f);
 #else
       const float sc = (float)tot;
 #endif
@@ -1601,8 +1685,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
         // m' = b1 m + (1 - b1) sc g, v' = b2 v + (1 - b2) sc^2 g^2 (Keras ApplyAdam on the
         // clipped gradient sc g, regrouped: the update is checked against float64 with a
         // tolerance), theta -= alpha m' / (sqrt(v') + eps)
-        const xa_f2 k1 = {sc * omb1, sc * omb1}, k2 = {(sc * sc) * omb2, (sc * sc) * omb2};
-        const xa_f2 al = {alpha, alpha}, ep = {p.adam.eps, p.adam.eps};
+        const xa_f2 k1 = {sc * XA_UF(uf.omb1, omb1), sc * XA_UF(uf.omb1, omb1)};
+        const xa_f2 k2 = {(sc * sc) * XA_UF(uf.omb2, omb2), (sc * sc) * XA_UF(uf.omb2, omb2)};
+        const xa_f2 al = {alpha, alpha}, ep = {XA_UF(uf.eps, p.adam.eps), XA_UF(uf.eps, p.adam.eps)};
         float th[4 * NQ4];
 #pragma unroll
         for (int q = 0; q < 4 * NQ4; ++q) th[q] = q < 16 ? wv[q] : q < NS ? rv[q - 16] : 0.0f;
@@ -1641,6 +1726,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     }
   }
 #undef XA_OUT
+#undef XA_UF
   XA_TRACE_CLK(b, 1);
   XA_TRACE_FLUSH(b);
   // theta / m / v out: every block holds the same final values, so block b stores the
