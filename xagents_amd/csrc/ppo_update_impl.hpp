@@ -20,6 +20,12 @@
 //        block), clip + Keras Adam with t = t0 + k + 1 on its register-resident slice
 //        of theta / m / v (ppo_tile.hpp PSlice), refresh the LDS weight tiles
 //   block 0 stores theta / m / v and the Adam step count at the end.
+// In the single-GPU column-form kernels (the 16-env headline among them) a step has ONE
+// workgroup-wide vote: phase B keeps every part of a pair column on one wave, combines the
+// parts lane to lane and publishes without a barrier or an LDS stage; a failed poll of
+// either phase raises the block's LDS abort word, which phase C's barrier then reads
+// (sticky_vote). The headline step is about 6.1 us (7.0 before; 104.5 us per 16-step
+// launch with its 7-us prologue, profiles/ppo_update_phase_b_ab.txt).
 // Data parallel (dp_world = W > 1, the DP template variant): phase 0's per-minibatch
 // advantage totals and, in every step, each block's phase-B slice are pushed to every
 // rank's IPC-mapped exchange block and summed in rank order from the own block (system-
@@ -293,6 +299,76 @@ XA_DEV bool poll_row(__amdgpu_buffer_rsrc_t r, const uint32_t (&off)[N], int n, 
       }
     }
   }
+}
+
+// lane `src`'s copy of an f64 (ds_bpermute: a lane-to-lane move through the LDS crossbar, no
+// LDS word involved; zero from a lane that is switched off)
+XA_DEV double lane_f64(double v, int src) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)(u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// poll_row whose rounds after the first load only the entries whose tag was not yet seen (a
+// seen entry keeps its value: a row word is rewritten once per step, so it cannot change
+// again before this block has consumed it). The first round, the abort-word and clock
+// checks on every 16th round and the sleep are poll_row's.
+template <int N>
+XA_DEV bool poll_row_missing(__amdgpu_buffer_rsrc_t r, const uint32_t (&off)[N], int n,
+                             unsigned tag, RowG (&v)[N], unsigned* ctl, unsigned epoch,
+                             int* status) {
+  {
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+      if (u < n) v[u] = ld_row(r, off[u]);
+    bool ok = true;
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+      if (u < n) ok = ok && row_ok(v[u], tag);
+    if (ok) return true;
+#ifndef XA_POLL_NOSLEEP
+    __builtin_amdgcn_s_sleep(XA_POLL_SLEEP);
+#endif
+  }
+  uint64_t t0 = 0;
+  for (unsigned it = 1;; ++it) {
+    const bool slow = (it & 15u) == 15u;
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+      if (u < n && !row_ok(v[u], tag)) v[u] = ld_row(r, off[u]);
+    const unsigned ab = slow ? __hip_atomic_load((gu32*)(ctl + kAbort), __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT)
+                             : 0u;
+    bool ok = true;
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+      if (u < n) ok = ok && row_ok(v[u], tag);
+    if (ok) return true;
+    if (!slow) {
+#ifndef XA_POLL_NOSLEEP
+      __builtin_amdgcn_s_sleep(XA_POLL_SLEEP);
+#endif
+      continue;
+    }
+    if (ab == epoch) return false;
+    {
+      const uint64_t now = wall_clock64();
+      if (t0 == 0) t0 = now;
+      else if (now - t0 > kSpinTicks) {
+        __hip_atomic_store((gu32*)(ctl + kAbort), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (status) __hip_atomic_store((gu32*)status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return false;
+      }
+    }
+  }
+}
+// (the column form's poll: XA_PHB_REPOLL picks the one above)
+template <bool MISSING, int N>
+XA_DEV bool poll_row_col(__amdgpu_buffer_rsrc_t r, const uint32_t (&off)[N], int n, unsigned tag,
+                         RowG (&v)[N], unsigned* ctl, unsigned epoch, int* status) {
+  if constexpr (MISSING) return poll_row_missing<N>(r, off, n, tag, v, ctl, epoch, status);
+  else return poll_row<N>(r, off, n, tag, v, ctl, epoch, status);
 }
 
 // poll_gran over tagged f64 pairs (d_tagged, above); entry u is polled when bit u of `valid`
@@ -579,6 +655,7 @@ struct UpdLds {
   int wx[4][kXcds];   // census: blocks per (wave of block ids, XCD)
   int xmem[256];      // this XCD's blocks, ascending block id (two-level)
   int xrank;          // this block's position among them
+  int abort;          // a poll of this block timed out (sticky_vote; zeroed in the prologue)
 #ifdef XA_TRACE
   unsigned trace[kTraceSteps * kTracePts];
 #endif
@@ -640,6 +717,29 @@ XA_DEV auto uni_ptid(int tid) {
   }
 }
 
+// The block's verdict on its polls where one of its threads may have timed out (every thread
+// then leaves), without the device library's __syncthreads_or (a DPP or-reduction per wave,
+// two readlanes, and tests on the block size and the work-item id whose masks the step loop
+// spills): a thread whose poll failed raises the block's LDS abort word -- the only store, and
+// only on that path -- and the vote is one barrier and one LDS read of a word that is never
+// reset inside a launch (a time-out ends the launch for this block). The word is the same
+// for every lane, so the first lane's copy makes the branch a scalar one.
+template <class LDS>
+XA_DEV int sticky_vote(LDS& U, bool bad) {
+  if (bad) U.abort = 1;
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(U.abort);
+}
+// the three pieces of the column-form step (kernel: kPhb*), each an A/B switch
+#ifndef XA_PHB_ABORT
+#define XA_PHB_ABORT 1
+#endif
+#ifndef XA_PHB_WAVE
+#define XA_PHB_WAVE 1
+#endif
+#ifndef XA_PHB_REPOLL
+#define XA_PHB_REPOLL 1
+#endif
 
 // TS = samples per tile (32; 16 when the minibatch has at most 16 tiles of 32: twice the
 // blocks, half the element-wise work per block and step); PRE = every tile input of the
@@ -665,6 +765,13 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
                                                           int n_mb_, int loc_) {
   constexpr bool FIX = BF == 3 || BF == 4;
   typedef FixShape<BF> FS;
+  // the single-GPU column-form kernels (the ones with the three step-loop copies, kForms):
+  // their votes on the step's polls read the block's abort word (sticky_vote), phase B
+  // combines a column's parts inside one wave, and its poll reloads only what is missing
+  constexpr bool kPhb = (BF == 1 || BF == 3) && !DP;
+  constexpr bool kPhbAbort = kPhb && XA_PHB_ABORT, kPhbWave = kPhb && XA_PHB_WAVE;
+  constexpr bool kPhbRepoll = kPhb && XA_PHB_REPOLL;
+  static_assert(!kPhb || TS == 16, "the column-form kernels run 16-sample tiles");
   // (the two-level-only kernels, BF 2 / 4, are never launched XCD-local: that mode's code
   // is compiled out of them -- it cost the C2 kernel 12 more scalar spills)
   const int K = FIX ? FS::K : K_, n_mb = FIX ? FS::NMB : n_mb_;
@@ -759,6 +866,9 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   const int t0 = *p.adam_step;
   for (int k = tid; k < K; k += 256)
     U.alpha[k] = adam_alpha(p.adam.lr, p.adam.beta1, p.adam.beta2, t0 + k + 1);
+  if constexpr (kPhbAbort) {
+    if (tid == 0) U.abort = 0;  // (ordered before the step loop by the barrier after phase 0)
+  }
   // with the inputs preloaded: all 256 threads gather the (step, sample) items and park each
   // advantage in LDS (U.red, free until phase B), then a wave per step sums them in the
   // lane-strided order of the loop below (bit-identical sums, all lanes busy in the gather)
@@ -1183,6 +1293,8 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
     uf.clip = uni_vreg(p.adam.clip_norm), uf.omb1 = uni_vreg(omb1), uf.omb2 = uni_vreg(omb2);
   }
 #define XA_UF(held, arg) (kUniF ? (held) : (arg))
+  // a vote of the step loop: the block's abort word (sticky_vote), or the library's
+#define XA_VOTE(bad) (kPhbAbort ? sticky_vote(U, bad) : __syncthreads_or(bad))
   PtAcc<OBS, A> acc;
   float w2r[16];  // dH1's B operand: W2 row 16 w + li, columns 16 lq .. (load_w2_rows)
   int k_tr = 0;  // the step the tile trace points belong to
@@ -1426,7 +1538,66 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
       // that order -- the flat path's arithmetic without its LDS staging pass
       const int parts_b = nc <= 128 ? min(4, 256 / max(nc, 1)) : 1;
       const bool col_b = !two_level && nc > 0 && parts_b > 1 && (G + parts_b - 1) / parts_b <= kBF;
-      if (col_b) {
+      [[maybe_unused]] bool bad_b = false;  // (kPhbWave) a phase-B poll of this thread failed
+      if constexpr (kPhbWave) {
+        // The column form with every part of a pair column in ONE wave (the host's
+        // col_b_everywhere holds, so col_b wherever nc > 0): wave v owns columns
+        // [v cpw, (v + 1) cpw) of the slice, cpw = 64 / parts_b (32, 21 or 16), and lane
+        // part * cpw + j of it polls and sums part `part` of column v cpw + j -- rows part,
+        // part + parts_b, ... in that order, in f64, as before. The lane of part 0 then
+        // fetches parts 1, 2, ... from lanes j + cpw, j + 2 cpw, ... (ds_bpermute: lane to
+        // lane, no LDS word written) and adds them in part order, converts to f32 and
+        // publishes: the sums of the LDS form bit for bit, without its U.red stage and
+        // without a barrier, so a wave with no column (and the lanes past the last part)
+        // goes straight on to phase C.
+        // No vote here: `bad_b` is carried into phase C's vote. A wave with a failed poll
+        // publishes nothing. Every block still leaves: a thread only fails a poll after
+        // the abort word (ws.ctl) was raised -- by itself at its time-out, or by the thread
+        // whose time-out it read there -- and every poller of the launch reads that word on
+        // each 16th round, so phase C's polls end in every block, this one included, and
+        // every thread reaches C's vote with the failure recorded.
+        const int t = uni_tid<kUniP>(tid), bl = t & 63;
+        const int bw = __builtin_amdgcn_readfirstlane(t >> 6);
+        const int cpw = parts_b == 2 ? 32 : parts_b == 3 ? 21 : 16;
+        if (nc > 0 && bw * cpw < nc) {
+          const int part = (bl >= cpw) + (bl >= 2 * cpw) + (bl >= 3 * cpw);
+          const int j = bl - part * cpw, c = bw * cpw + j;
+          double t0 = 0.0, t1 = 0.0;
+          if (part < parts_b && c < nc) {
+            uint32_t off[kBF];
+            RowG x[kBF];
+            int n = 0;
+#pragma unroll
+            for (int u = 0; u < kBF; ++u) {
+              const int r = part + parts_b * u;
+              off[u] = r < G ? rows_o + (uint32_t)((size_t)r * NP2 + c0 + c) * kRowPB : 0u;
+              n += r < G;
+            }
+            bad_b = !poll_row_col<kPhbRepoll, kBF>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
+#pragma unroll
+            for (int u = 0; u < kBF; ++u)
+              if (u < n) {
+                t0 += (double)row_v0(x[u]);
+                t1 += (double)row_v1(x[u]);
+              }
+          }
+          // (all 64 lanes: ds_bpermute reads zero from a lane that is switched off)
+          const bool wave_bad = __ballot(bad_b) != 0ull;
+          double s0 = 0.0, s1 = 0.0;
+          s0 += t0;
+          s1 += t1;
+#pragma unroll
+          for (int q = 1; q < 4; ++q)
+            if (q < parts_b) {
+              s0 += lane_f64(t0, j + q * cpw);
+              s1 += lane_f64(t1, j + q * cpw);
+            }
+          if (!wave_bad && bl < cpw && c < nc) {
+            const float g0 = (float)s0, g1 = (float)s1;
+            emit(c, g0, g1);
+          }
+        }
+      } else if (col_b) {
         double t0 = 0.0, t1 = 0.0;
         bool bad = false;
         if (uni_tid<kUniP>(tid) < parts_b * nc) {
@@ -1440,7 +1611,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
             off[u] = r < G ? rows_o + (uint32_t)((size_t)r * NP2 + c0 + c) * kRowPB : 0u;
             n += r < G;
           }
-          bad = !poll_row<kBF>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
+          bad = !poll_row_col<kPhbRepoll, kBF>(rows_r, off, n, tag, x, ws.ctl, epoch, p.status);
 #pragma unroll
           for (int u = 0; u < kBF; ++u)
             if (u < n) {
@@ -1450,7 +1621,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
           U.red[(part * nc + c) * 2] = t0;
           U.red[(part * nc + c) * 2 + 1] = t1;
         }
-        if (__syncthreads_or(bad)) return;
+        if (XA_VOTE(bad)) return;
         for (int c = uni_tid<kUniP>(tid); c < nc; c += 256) {
           double s0 = 0.0, s1 = 0.0;
           for (int part = 0; part < parts_b; ++part) {
@@ -1641,6 +1812,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
         for (int q = 0; q < RPT; ++q)
           off[8 + q] = g_o + (uint32_t)((ps.rx[q] >= 0 ? ps.rx[q] / 2 : 0) * kRowPB);
         bad = !poll_row<NG>(g_r, off, NG, tag, x, ws.ctl, epoch, p.status);
+        if constexpr (kPhbWave) bad = bad || bad_b;  // phase B's poll: one vote for both
         XA_STAMP(46);
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
@@ -1665,7 +1837,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
         const double ws = xa_wave_sum_f64(s0 + s1);
         if ((uni_tid<kUniP>(tid) & 63) == 0) U.wsum[w] = ws;
       }
-      if (__syncthreads_or(bad)) return;
+      if (XA_VOTE(bad)) return;
       XA_STAMP(47);
       XA_TRACE_PT(b, k, 4);
 #ifndef XA_ABL_CNORM
@@ -1727,6 +1899,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(XaPpoUpdateArgs p, Ws w
   }
 #undef XA_OUT
 #undef XA_UF
+#undef XA_VOTE
   XA_TRACE_CLK(b, 1);
   XA_TRACE_FLUSH(b);
   // theta / m / v out: every block holds the same final values, so block b stores the
@@ -1839,6 +2012,9 @@ bool col_b_everywhere(int G, int P) {
     if (nc <= 0) continue;
     const int parts = nc <= 128 ? min(4, 256 / nc) : 1;
     if (!(parts > 1 && (G + parts - 1) / parts <= kBF)) return false;
+    // ... with every part of a column in one wave: four waves of 64 / parts columns each
+    // hold the slice (all but nc = 85 with 3 parts, e.g. P = 5061 on 30 blocks)
+    if (nc > 4 * (64 / parts)) return false;
   }
   return true;
 }
