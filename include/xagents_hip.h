@@ -621,6 +621,15 @@ int xa_dqn_td_grad(const float* q, const float* q_next_target, const float* q_ne
                    int n_actions, float gamma, float huber_delta, float* dq, float* loss,
                    int* adam_step, void* stream);
 
+/* xa_dqn_td_grad (the same kernel) for prioritized replay, both pointers optional and both
+ * NULL the bytes of xa_dqn_td_grad: is_weights [batch] (in) multiplies dq[b][a_b] and loss[b]
+ * by w_b, one f32 multiply after the unweighted value; td_abs [batch] (out) =
+ * |y - q[b][a_b]|, unclipped with Huber as well (the new priority, xa_per_update). */
+int xa_dqn_td_grad_w(const float* q, const float* q_next_target, const float* q_next_online,
+                     const int* actions, const float* rewards, const float* dones, int batch,
+                     int n_actions, float gamma, float huber_delta, float* dq, float* loss,
+                     int* adam_step, const float* is_weights, float* td_abs, void* stream);
+
 /* The Q head (the last dense layer, N <= 8 actions: xa_gemm's row-dot shape) with DQN's
  * per-row step fused into the same launch. mode 0: actions[m] = first argmax of row m
  * (xa_dqn_act's greedy branch); mode 1: the head is the TARGET network's over s', and row b
@@ -930,6 +939,62 @@ int xa_sac_td_grad(const float* v1, const float* v2, const float* tv1, const flo
                    const float* logp_next, const float* log_alpha, const float* rewards,
                    const float* dones, int batch, float gamma, float huber_delta, float* dv1,
                    float* dv2, float* loss, void* stream);
+
+/* xa_sac_td_grad (the same kernel) for prioritized replay, both pointers optional and both
+ * NULL the bytes of xa_sac_td_grad: is_weights [batch] (in) multiplies dv_i[b] and loss[b] by
+ * w_b, one f32 multiply after the unweighted value; td_abs [batch] (out) =
+ * 0.5 (|v1 - y| + |v2 - y|), unclipped with Huber as well. */
+int xa_sac_td_grad_w(const float* v1, const float* v2, const float* tv1, const float* tv2,
+                     const float* logp_next, const float* log_alpha, const float* rewards,
+                     const float* dones, int batch, float gamma, float huber_delta, float* dv1,
+                     float* dv2, float* loss, const float* is_weights, float* td_abs,
+                     void* stream);
+
+/* Prioritized experience replay (https://arxiv.org/abs/1511.05952) over the replay rings'
+ * global slots env * capacity + row (csrc/per.hip; csrc/per_terms.hpp states the arithmetic).
+ * The priorities live in a 64-ary sum tree: leaves [n_leaves] float, priority^alpha already
+ * exponentiated and 0 for a slot never written; above them levels of ceil(n / 64) double
+ * nodes until a level has one node (the root), all in ONE double array `nodes`
+ * [xa_per_tree_nodes(n_leaves)], level 1 first, the root last. A node is always the sum of its
+ * 64 children in xa_wave_sum_f64's order (a missing child counts 0), recomputed and never
+ * adjusted by a delta. mark, update and sample are one workgroup and one launch each.
+ *
+ * xa_per_rebuild: every node from the leaves (one launch per level).
+ *
+ * xa_per_mark: for each env e, leaf e * capacity + count[e] % capacity = (*max_priority)^alpha,
+ * then its ancestors. count is the ring's device counter BEFORE the append (enqueue in front of
+ * the env-step launch); the rule covers both ring kinds, ReplayBuffer2's row-0 overwrite once
+ * count saturates at capacity included. n_leaves = n_envs * capacity.
+ *
+ * xa_per_sample: batch stratified draws. Sample j descends from the root with the target
+ * t_j = ((double)j + (double)u_j) / batch * root, u_j = u_in[j] when given, else xa_u01 of
+ * Philox4x32-10 at (j, *rng_counter), key seed; u_out (optional) receives the u_j used. At a
+ * node, with S_i the inclusive f64 prefix sums of its children c_i, the child is the first with
+ * t < S_i and c_i > 0 (none, through rounding: the last with c_i > 0), and t -= S_{i-1}: a leaf
+ * holding 0 is never returned while the root is > 0. Outputs: slots [batch] int64 (global),
+ * leaf_p [batch] (the leaves found), weights [batch] = w_j / max_j w_j with
+ * w_j = (N leaf_j / root)^(-*beta) in f64, stored as float -- the BATCH-MAX normalisation
+ * (the largest weight of every batch is 1; not the maximum over the whole buffer).
+ * N = sum_e min(count[e], capacity) and *beta are read on device, so a captured launch sees
+ * the current fill and the annealed beta. The tree must hold a priority (root > 0).
+ *
+ * xa_per_update: leaf[slots[b]] = powf(td_abs[b] + eps, alpha) for the batch items, then their
+ * ancestors level by level; *max_priority = max(*max_priority, max_b (td_abs[b] + eps)). A
+ * slot outside [0, n_leaves) is skipped. Of the items that list one slot the LAST stores the
+ * leaf (one writer per leaf, so the launch is deterministic); every item counts towards
+ * max_priority. */
+size_t xa_per_tree_nodes(int64_t n_leaves);
+int xa_per_rebuild(const float* leaves, double* nodes, int64_t n_leaves, void* stream);
+int xa_per_mark(float* leaves, double* nodes, int64_t n_leaves, const int64_t* count, int n_envs,
+                int64_t capacity, const float* max_priority, float alpha, void* stream);
+int xa_per_sample(const float* leaves, const double* nodes, int64_t n_leaves,
+                  const int64_t* count, int n_envs, int64_t capacity, int batch,
+                  const float* u_in, const uint64_t* rng_counter, uint64_t seed,
+                  const float* beta, int64_t* slots, float* leaf_p, float* weights,
+                  float* u_out, void* stream);
+int xa_per_update(float* leaves, double* nodes, int64_t n_leaves, const int64_t* slots,
+                  const float* td_abs, int batch, float alpha, float eps, float* max_priority,
+                  void* stream);
 
 /* Actor loss rows loss[b] = alpha logp - min(q1, q2) (optional) and the seeds of the critics'
  * input-gradient passes, d(-mean Qmin)/dq: -1 / batch on the critic holding the minimum (ties:

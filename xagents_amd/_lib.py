@@ -508,6 +508,11 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
          c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    'xa_dqn_td_grad_w': (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     'xa_ring_scatter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'xa_ring_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'xa_ring_gather_fields': (c_int, [c_void_p, c_void_p]),
@@ -562,6 +567,27 @@ _SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
          c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    'xa_sac_td_grad_w': (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    'xa_per_tree_nodes': (ctypes.c_size_t, [c_int64]),
+    'xa_per_rebuild': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    'xa_per_mark': (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_float, c_void_p],
+    ),
+    'xa_per_sample': (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+         c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    'xa_per_update': (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p,
+         c_void_p],
     ),
     'xa_sac_actor_seed': (
         c_int,

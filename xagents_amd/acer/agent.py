@@ -77,8 +77,13 @@ class ACER(A2C):
         grad_norm=0.5,
         use_graph=True,
         redraw_replays=False,
+        prioritized=False,
         **kwargs,
     ):
+        if prioritized:
+            raise NotImplementedError(
+                'ACER has no prioritized replay path: it replays whole trajectories drawn by '
+                'its own Poisson rule (DQN and SAC have one)')
         OnPolicy.__init__(self, envs, model, **kwargs)
         self.redraw_replays = redraw_replays
         self._replay_count = None

@@ -687,14 +687,56 @@ class OffPolicy(BaseAgent, ABC):
         envs,
         model,
         buffers,
+        prioritized=False,
+        per_alpha=0.6,
+        per_beta=0.4,
+        per_beta_steps=100000,
+        per_eps=1e-6,
         **kwargs,
     ):
+        self._check_prioritized(prioritized)
         super(OffPolicy, self).__init__(envs, model, **kwargs)
         assert len(envs) == len(buffers), (
             f'Expected equal env and replay buffer sizes, got {self.n_envs} '
             f'and {len(buffers)}'
         )
         self.buffers = buffers
+        self.prioritized = bool(prioritized)
+        self.per_alpha, self.per_eps = per_alpha, per_eps
+        self.per_beta = self.per_beta_start = per_beta
+        self.per_beta_steps = per_beta_steps
+        self.per = None  # the PrioritizedSampler, built with the rings (_setup_offpolicy)
+
+    # ---- prioritized replay (xagents_amd/per.py) ------------------------------------
+    # agents whose learner phase samples through the PrioritizedSampler (DQN, SAC)
+    _supports_prioritized = False
+
+    @classmethod
+    def _check_prioritized(cls, prioritized):
+        """Refuse prioritized=True where no path takes it, before anything is built."""
+        if not prioritized:
+            return
+        if not cls._supports_prioritized:
+            raise NotImplementedError(
+                f'{cls.__name__} has no prioritized replay path (DQN and SAC have; the fused '
+                f'DDPG / TD3 launch gathers its batch internally)')
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            raise NotImplementedError(
+                'prioritized replay has no data-parallel path: every rank would need the '
+                'union of the ranks\' priorities')
+
+    def _per_anneal(self):
+        """beta grows linearly from per_beta to 1 over per_beta_steps agent steps; the host
+        writes it into the sampler's device scalar (outside any captured phase) when it
+        moves."""
+        if self.per is None:
+            return
+        frac = min(1.0, self.steps / self.per_beta_steps) if self.per_beta_steps > 0 else 1.0
+        beta = self.per_beta_start + (1.0 - self.per_beta_start) * frac
+        if beta != self.per_beta:
+            self.per_beta = beta
+            self.per.set_beta(beta)
 
     # ---- device env stepping + replay append (step_envs(store_in_buffers=True)) ----
     _STATS_ROWS = 64
@@ -719,6 +761,10 @@ class OffPolicy(BaseAgent, ABC):
         env = self.envs
         self.replay = DeviceReplay(self.buffers, env.obs_shape, env.obs_dtype, act_shape,
                                    act_dtype, self.device)
+        if self.prioritized:
+            from xagents_amd.per import PrioritizedSampler
+            self.per = PrioritizedSampler(self.replay, self.per_alpha, self.per_beta,
+                                          self.per_eps, self.seed or 0)
         self._step_args = XaReplayStepArgs()
         env.fill_step_args(self._step_args)
         n, K = self.n_envs, self._STATS_ROWS
@@ -741,6 +787,8 @@ class OffPolicy(BaseAgent, ABC):
         r = self._st_row
         a.out_dones = self._st_done[r].data_ptr()
         a.done_epret = self._st_epret[r].data_ptr()
+        if store and self.per is not None:
+            self.per.mark()  # reads the ring counters before the step's append
         self.envs.step_into(a, actions)
         if store:
             self.replay.appended()

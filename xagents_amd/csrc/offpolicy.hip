@@ -59,12 +59,15 @@ __global__ void dqn_act_kernel(const float* __restrict__ q, int n, int A,
 
 // DQN.get_targets + the loss gradient (dqn/agent.py:118-171), td_terms.hpp's dqn_target and
 // dqn_td on v' = double ? Qt(s')[argmax Q(s')] : max_a Qt(s') (minimize on a [B] loss sums);
-// dQ is zero off the action (y copies Q there)
+// dQ is zero off the action (y copies Q there). is_weights / td_abs (prioritized replay, both
+// optional): td_terms.hpp's weighted / td_abs_of
 __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restrict__ q_next_t,
                               const float* __restrict__ q_next_o, const int* __restrict__ act,
                               const float* __restrict__ rew, const float* __restrict__ done,
                               int B, int A, float gamma, float huber, float* __restrict__ dq,
-                              float* __restrict__ loss, int* __restrict__ adam_step) {
+                              float* __restrict__ loss, int* __restrict__ adam_step,
+                              const float* __restrict__ is_weights,
+                              float* __restrict__ td_abs) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (adam_step && b == 0) adam_step[0] += 1;  // the update's t += 1, one launch fewer
   if (b >= B) return;
@@ -78,10 +81,13 @@ __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restri
   }
   const float y = xa_td::dqn_target(v, done[b], gamma, rew[b]);
   const int ab = act[b];
+  const float diff = y - q[(size_t)b * A + ab];
   float dqa, l;
-  xa_td::dqn_td(y - q[(size_t)b * A + ab], huber, A, dqa, l);
+  xa_td::dqn_td(diff, huber, A, dqa, l);
+  dqa = xa_td::weighted(dqa, is_weights, b);
   for (int a = 0; a < A; ++a) dq[(size_t)b * A + a] = a == ab ? dqa : 0.0f;
-  if (loss) loss[b] = l;
+  if (loss) loss[b] = xa_td::weighted(l, is_weights, b);
+  if (td_abs) td_abs[b] = xa_td::td_abs_of(diff);
 }
 
 // ring[slot[i]] <- src[i] for n_items items of item_bytes each (append)
@@ -312,19 +318,30 @@ extern "C" int xa_dqn_act(const float* q, int n, int n_actions, const int* rando
   return 0;
 }
 
-extern "C" int xa_dqn_td_grad(const float* q, const float* q_next_target,
-                              const float* q_next_online, const int* actions,
-                              const float* rewards, const float* dones, int batch, int n_actions,
-                              float gamma, float huber_delta, float* dq, float* loss,
-                              int* adam_step, void* stream) {
+extern "C" int xa_dqn_td_grad_w(const float* q, const float* q_next_target,
+                                const float* q_next_online, const int* actions,
+                                const float* rewards, const float* dones, int batch,
+                                int n_actions, float gamma, float huber_delta, float* dq,
+                                float* loss, int* adam_step, const float* is_weights,
+                                float* td_abs, void* stream) {
   XA_CHECK_ARG(q && q_next_target && actions && rewards && dones && dq && batch > 0 &&
                    n_actions > 0,
                "xa_dqn_td_grad: bad arguments");
   hipLaunchKernelGGL(dqn_td_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, q,
                      q_next_target, q_next_online, actions, rewards, dones, batch, n_actions,
-                     gamma, huber_delta, dq, loss, adam_step);
+                     gamma, huber_delta, dq, loss, adam_step, is_weights, td_abs);
   XA_CHECK_LAUNCH("xa_dqn_td_grad");
   return 0;
+}
+
+extern "C" int xa_dqn_td_grad(const float* q, const float* q_next_target,
+                              const float* q_next_online, const int* actions,
+                              const float* rewards, const float* dones, int batch, int n_actions,
+                              float gamma, float huber_delta, float* dq, float* loss,
+                              int* adam_step, void* stream) {
+  return xa_dqn_td_grad_w(q, q_next_target, q_next_online, actions, rewards, dones, batch,
+                          n_actions, gamma, huber_delta, dq, loss, adam_step, nullptr, nullptr,
+                          stream);
 }
 
 extern "C" int xa_ring_scatter(const void* src, void* ring, const int64_t* slots, int n_items,

@@ -41,23 +41,27 @@ __global__ __launch_bounds__(kRowBlock) void sac_sample_kernel(
 }
 
 // twin critics against the soft target: xa_critic_td_grad's kernel with
-// min(tv1, tv2) - alpha logp' in the target critic's place
+// min(tv1, tv2) - alpha logp' in the target critic's place. is_weights / td_abs (prioritized
+// replay, both optional): td_terms.hpp's weighted / td_abs_of, the twins' mean
 __global__ __launch_bounds__(kRowBlock) void sac_td_kernel(
     const float* __restrict__ v1, const float* __restrict__ v2, const float* __restrict__ tv1,
     const float* __restrict__ tv2, const float* __restrict__ logp_next,
     const float* __restrict__ log_alpha, const float* __restrict__ rew,
     const float* __restrict__ done, int B, float gamma, float huber, float* __restrict__ dv1,
-    float* __restrict__ dv2, float* __restrict__ loss) {
+    float* __restrict__ dv2, float* __restrict__ loss, const float* __restrict__ is_weights,
+    float* __restrict__ td_abs) {
   const int b = blockIdx.x * kRowBlock + threadIdx.x;
   if (b >= B) return;
   const float y = xa_sac::critic_target(rew[b], done[b], gamma, tv1[b], tv2[b],
                                         xa_sac::alpha_of(log_alpha), logp_next[b]);
+  const float e1 = v1[b] - y, e2 = v2[b] - y;
   float d1, d2;
-  float l = xa_td::td_term(v1[b] - y, huber, d1);
-  l = l + xa_td::td_term(v2[b] - y, huber, d2);
-  dv1[b] = d1;
-  dv2[b] = d2;
-  if (loss) loss[b] = l;
+  float l = xa_td::td_term(e1, huber, d1);
+  l = l + xa_td::td_term(e2, huber, d2);
+  dv1[b] = xa_td::weighted(d1, is_weights, b);
+  dv2[b] = xa_td::weighted(d2, is_weights, b);
+  if (loss) loss[b] = xa_td::weighted(l, is_weights, b);
+  if (td_abs) td_abs[b] = 0.5f * (xa_td::td_abs_of(e1) + xa_td::td_abs_of(e2));
 }
 
 // ONE workgroup whatever B is, so the temperature gradient's sum has one order: thread t
@@ -123,19 +127,28 @@ extern "C" int xa_sac_sample(const float* mean, int64_t ld_mean, const float* lo
   return 0;
 }
 
-extern "C" int xa_sac_td_grad(const float* v1, const float* v2, const float* tv1,
-                              const float* tv2, const float* logp_next, const float* log_alpha,
-                              const float* rewards, const float* dones, int batch, float gamma,
-                              float huber_delta, float* dv1, float* dv2, float* loss,
-                              void* stream) {
+extern "C" int xa_sac_td_grad_w(const float* v1, const float* v2, const float* tv1,
+                                const float* tv2, const float* logp_next, const float* log_alpha,
+                                const float* rewards, const float* dones, int batch, float gamma,
+                                float huber_delta, float* dv1, float* dv2, float* loss,
+                                const float* is_weights, float* td_abs, void* stream) {
   XA_CHECK_ARG(v1 && v2 && tv1 && tv2 && logp_next && log_alpha && rewards && dones && dv1 &&
                    dv2 && batch > 0,
                "xa_sac_td_grad: bad arguments");
   hipLaunchKernelGGL(sac_td_kernel, dim3(row_blocks(batch)), dim3(kRowBlock), 0,
                      (hipStream_t)stream, v1, v2, tv1, tv2, logp_next, log_alpha, rewards, dones,
-                     batch, gamma, huber_delta, dv1, dv2, loss);
+                     batch, gamma, huber_delta, dv1, dv2, loss, is_weights, td_abs);
   XA_CHECK_LAUNCH("xa_sac_td_grad");
   return 0;
+}
+
+extern "C" int xa_sac_td_grad(const float* v1, const float* v2, const float* tv1,
+                              const float* tv2, const float* logp_next, const float* log_alpha,
+                              const float* rewards, const float* dones, int batch, float gamma,
+                              float huber_delta, float* dv1, float* dv2, float* loss,
+                              void* stream) {
+  return xa_sac_td_grad_w(v1, v2, tv1, tv2, logp_next, log_alpha, rewards, dones, batch, gamma,
+                          huber_delta, dv1, dv2, loss, nullptr, nullptr, stream);
 }
 
 extern "C" int xa_sac_actor_seed(const float* q1, const float* q2, const float* logp,

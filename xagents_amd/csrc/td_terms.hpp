@@ -56,6 +56,14 @@ XA_DEV void dqn_td(float diff, float huber, int A, float& dqa, float& l) {
   dqa = -d / (float)A;
 }
 
+// Prioritized replay (per.hip): the sample's importance weight scales a gradient seed or a
+// loss row in ONE f32 multiply after the unweighted value (no weights: the value itself, the
+// unweighted bits), and the new priority's |TD error| is the unclipped one, with Huber too.
+XA_DEV float weighted(float x, const float* is_weights, int b) {
+  return is_weights ? x * is_weights[b] : x;
+}
+XA_DEV float td_abs_of(float e) { return fabsf(e); }
+
 // standard normal from Philox4x32-10 (Box-Muller on two 24-bit uniforms, u1 in (0, 1])
 XA_DEV float philox_normal(uint32_t i, uint32_t j, uint64_t ctr, uint64_t seed) {
   const xa_u4 r = xa_philox(i, j, (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed,

@@ -550,6 +550,8 @@ class DDPG(OffPolicy):
         a = self._step_args
         self.replay.fill_step_args(a, actions)
         a.out_dones, a.done_epret = self._stage_ptrs
+        if self.per is not None:
+            self.per.mark()  # (SAC, prioritized) reads the ring counters before the append
         self.envs.step_into(a, actions)
 
     def train_step(self):

@@ -14,6 +14,13 @@ train_step (dqn/agent.py:182-197), all on device except the reference's host RNG
                          layer's step inside its weight-gradient GEMM (xa_gemm_adam, no
                          gradient round trip), the other layers' via xa_clip_adam
 at_step_end: hard target copy when steps % target_sync_steps == 0 (xa_polyak, tau 1).
+
+prioritized=True (xagents_amd/per.py; NOT a parity mode: the reference samples uniformly, and
+its RNG streams are not consumed by the draw): the learner phase becomes
+    xa_per_sample (slots, weights on device) -> xa_ring_gather from the device slots ->
+    forward -> xa_dqn_td_grad_w (dq and loss times the weight, |TD error| out) ->
+    xa_per_update -> backward -> Adam
+with no host slot draw and no staging; the Q head's TD step takes the separate launch.
 """
 import os
 
@@ -29,7 +36,14 @@ from xagents_amd.layers import LayerExecutor, adam_apply
 
 
 class DQN(OffPolicy):
-    """Playing Atari with Deep Reinforcement Learning https://arxiv.org/abs/1312.5602"""
+    """Playing Atari with Deep Reinforcement Learning https://arxiv.org/abs/1312.5602
+
+    prioritized / per_alpha / per_beta / per_beta_steps / per_eps (OffPolicy): proportional
+    prioritized replay, sampled on the device. beta anneals linearly to 1 over per_beta_steps
+    agent steps. Not a parity mode: the reference has no such sampler and its RNG streams are
+    not consumed by the draw. The batch's weights are at agent.per.weights."""
+
+    _supports_prioritized = True
 
     def __init__(
         self,
@@ -173,8 +187,12 @@ class DQN(OffPolicy):
 
     def concat_buffer_samples(self):
         """One sampled batch gathered from the device rings in the reference's index
-        order: [states, actions, rewards, dones, new_states] (base.py:344-368)."""
-        slots = self.replay.upload_slots(self.replay.sample_slots())
+        order: [states, actions, rewards, dones, new_states] (base.py:344-368); prioritized:
+        the sampler's draw (its weights at self.per.weights)."""
+        if self.per is not None:
+            slots = self.per.sample()
+        else:
+            slots = self.replay.upload_slots(self.replay.sample_slots())
         B = self.batch_size
         self.replay.gather(slots, self.xb[:B], self.b_act, self.b_rew, self.b_done,
                            self.xb[B:])
@@ -185,12 +203,21 @@ class DQN(OffPolicy):
         Adam reads it after the backward)."""
         B = self.batch_size
         q_all = self.ex_online.forward(self.xb if self.double else self.xb[:B])[0]
-        if self._head_fused():
+        if self._head_fused() and self.per is None:
             # the TD target and its gradient ride in the target head's launch (mode 1)
             self.ex_target.forward(self.xb[B:], head=self._head_args('td'))
             return
         q_next_t = self.ex_target.forward(self.xb[B:])[0]
         q_next_o = q_all[B:].data_ptr() if self.double else None
+        if self.per is not None:
+            # the fused head carries no weights: the separate launch, weighted, |TD error| out
+            call('xa_dqn_td_grad_w', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
+                 self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
+                 self.n_actions, kernels._f32(self.gamma),
+                 kernels._f32(self.huber_delta or 0.0), self.dq.data_ptr(),
+                 self.td_loss.data_ptr(), self.model.optimizer.iterations.data_ptr(),
+                 self.per.weights.data_ptr(), self.per.td_abs.data_ptr(), stream())
+            return
         call('xa_dqn_td_grad', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
              self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
              self.n_actions, kernels._f32(self.gamma), kernels._f32(self.huber_delta or 0.0),
@@ -298,6 +325,7 @@ class DQN(OffPolicy):
 
     def at_step_start(self):
         self.update_epsilon()
+        self._per_anneal()
 
     def train_step(self):
         """dqn/agent.py:182-197"""
@@ -312,6 +340,9 @@ class DQN(OffPolicy):
         self.get_actions()
         self._env_step(self.actions)
         self.steps += self.n_envs
+        if self.per is not None:
+            self._run_learn()  # the draw is the phase's first launch: nothing to stage
+            return
         # host index draw in the reference's order, then the device learner phase (its
         # gather reads the staged slots from mapped pinned memory: no upload launch;
         # XA_PINNED_SLOTS=0: the upload copy)
@@ -341,6 +372,14 @@ class DQN(OffPolicy):
         """gather the sampled batch -> TD gradient -> CNN backward -> Keras Adam."""
         B = self.batch_size
         r = self.replay
+        if self.per is not None:
+            # sample -> gather from the device slots -> weighted TD -> priorities -> update
+            r.gather(self.per.sample(), self.xb[:B], self.b_act, self.b_rew, self.b_done,
+                     self.xb[B:])
+            self._td_grad()
+            self.per.update()
+            self._apply()
+            return
         src = (r.stage_ptr(), r.slots.numel()) if self._pinned_slots() else r.slots
         r.gather(src, self.xb[:B], self.b_act, self.b_rew, self.b_done, self.xb[B:])
         if self._pinned_slots() and self._stage_early() and \
