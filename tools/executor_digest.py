@@ -23,7 +23,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
-from xagents_amd import A2C, ACER, DDPG, DQN, PPO, TD3, TRPO  # noqa: E402
+from xagents_amd import A2C, ACER, DDPG, DQN, PPO, SAC, TD3, TRPO  # noqa: E402
 from xagents_amd.envs import create_envs  # noqa: E402
 from xagents_amd.utils.common import create_buffers, create_model  # noqa: E402
 
@@ -32,7 +32,9 @@ STEPS = 4
 BUFFERS = ('obs_buf', 'b_act', 'b_logp', 'b_val', 'b_ent', 'b_rew', 'b_done', 'b_epret',
            'b_ret', 'next_val', 'batch_states', 'g_act', 'g_mu', 'g_rew', 'g_done', 'r_frames',
            'r_mu', 'r_act', 'r_rew', 'r_done', 's_frames', 's_mu', 's_act', 's_rew', 's_done',
-           'dq', 'td_loss', 'dv1', 'dv2', 'critic_loss', 'noise')
+           'dq', 'td_loss', 'dv1', 'dv2', 'critic_loss', 'noise', 'logp', 'logp_next', 'eps',
+           'eps_next', 'dq1', 'dq2', 'actor_loss', 'dmean', 'dlog_std')
+PER_ARRAYS = ('leaves', 'nodes', 'slots', 'weights', 'max_priority', 'counter')
 
 
 def seed_host(s):
@@ -65,16 +67,23 @@ def acer(use_graph):
                 replay_ratio=2, grad_norm=10.0, use_graph=use_graph)
 
 
-def dqn(learn_graph, fused_head=True, **agent_kw):
-    # XA_DQN_FUSED_HEAD=0: xa_dqn_act / xa_dqn_td_grad launches instead of xa_dqn_head
-    if fused_head:
-        os.environ.pop('XA_DQN_FUSED_HEAD', None)
-    else:
-        os.environ['XA_DQN_FUSED_HEAD'] = '0'
-    if learn_graph:
-        os.environ['XA_DQN_LEARN_GRAPH'] = '1'
-    else:
-        os.environ.pop('XA_DQN_LEARN_GRAPH', None)
+def knobs(**values):
+    """Set each XA_* knob to its value, or clear it (None: the default)."""
+    for name, value in values.items():
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+
+
+def dqn(learn_graph, fused_head=True, upload=False, stage_late=False, **agent_kw):
+    # XA_DQN_FUSED_HEAD=0: xa_dqn_act / xa_dqn_td_grad launches instead of xa_dqn_head;
+    # XA_PINNED_SLOTS=0: the sampled slots uploaded, not staged; XA_DQN_STAGE_EARLY=0: the
+    # staged slots reported read behind the whole learner phase
+    knobs(XA_DQN_FUSED_HEAD=None if fused_head else '0',
+          XA_DQN_LEARN_GRAPH='1' if learn_graph else None,
+          XA_PINNED_SLOTS='0' if upload else None,
+          XA_DQN_STAGE_EARLY='0' if stage_late else None)
     envs = create_envs('PongNoFrameskip-v4', 2, device=DEV, seed=3)
     model = create_model(envs, 'dqn', 'model', seed=9, device=DEV)
     agent = DQN(envs, model, create_buffers('dqn', 40, 4, 2, initial_size=20), seed=2,
@@ -83,13 +92,12 @@ def dqn(learn_graph, fused_head=True, **agent_kw):
     return agent
 
 
-def ddpg(kind, fused=True, **agent_kw):
+def ddpg(kind, fused=True, upload=False, graph=False, **agent_kw):
     # XA_TD3_FUSED=0: the layer executor with xa_critic_td_grad, xa_noisy_actions and xa_polyak
-    # instead of the persistent xa_td3_update / xa_td3_act launches
-    if fused:
-        os.environ.pop('XA_TD3_FUSED', None)
-    else:
-        os.environ['XA_TD3_FUSED'] = '0'
+    # instead of the persistent xa_td3_update / xa_td3_act launches; XA_TD3_STAGED_SLOTS=0: the
+    # fused step's slots uploaded, not staged; XA_TD3_GRAPH=1: the fused step replayed
+    knobs(XA_TD3_FUSED=None if fused else '0', XA_TD3_STAGED_SLOTS='0' if upload else None,
+          XA_TD3_GRAPH='1' if graph else None)
     n = 4
     envs = create_envs('BipedalWalker-v3', n, mode='dynamics', device=DEV, seed=4)
     kw = dict(seed=7, device=DEV, optimizer_kwargs=dict(learning_rate=1e-3))
@@ -98,6 +106,19 @@ def ddpg(kind, fused=True, **agent_kw):
     bufs = create_buffers(kind, 64 * n, 2 * n, n, initial_size=8 * n)
     agent = (TD3 if kind == 'td3' else DDPG)(envs, actor, critic, bufs, seed=3, quiet=True,
                                              gradient_steps=1, **agent_kw)
+    agent.fill_buffers()
+    return agent
+
+
+def sac(use_graph=True, **agent_kw):
+    n = 4
+    envs = create_envs('Pendulum-v1', n, device=DEV, seed=4)
+    kw = dict(seed=7, device=DEV, optimizer_kwargs=dict(learning_rate=1e-3))
+    actor = create_model(envs, 'sac', 'actor_model', **kw)
+    critic = create_model(envs, 'sac', 'critic_model', **kw)
+    bufs = create_buffers('sac', 64 * n, 2 * n, n, initial_size=8 * n)
+    agent = SAC(envs, actor, critic, bufs, seed=3, quiet=True, gradient_steps=1, **agent_kw)
+    agent.use_graph = use_graph  # False: every phase launched directly
     agent.fill_buffers()
     return agent
 
@@ -131,6 +152,14 @@ CASES = [
     ('td3_walker_executor', lambda: ddpg('td3', fused=False)),
     ('ddpg_walker_executor', lambda: ddpg('ddpg', fused=False)),
     ('td3_walker_executor_huber', lambda: ddpg('td3', fused=False, huber_delta=0.5)),
+    ('sac_pendulum_graph', lambda: sac()),
+    ('sac_pendulum_eager', lambda: sac(use_graph=False)),
+    ('sac_pendulum_prioritized', lambda: sac(prioritized=True)),
+    ('dqn_pong_prioritized', lambda: dqn(True, prioritized=True)),
+    ('dqn_pong_upload', lambda: dqn(True, upload=True)),
+    ('dqn_pong_stage_late', lambda: dqn(False, stage_late=True)),
+    ('td3_walker_upload', lambda: ddpg('td3', upload=True)),
+    ('td3_walker_graph', lambda: ddpg('td3', graph=True)),
 ]
 
 
@@ -149,6 +178,10 @@ def arrays(agent):
         t = getattr(agent, name, None)
         if isinstance(t, torch.Tensor):
             yield name, t
+    per = getattr(agent, 'per', None)
+    if per is not None:
+        for name in PER_ARRAYS:
+            yield f'per.{name}', getattr(per, name)
 
 
 def main():

@@ -680,3 +680,17 @@ else:
 
 def call(name, *args):
     check(getattr(load(), name)(*args), name)
+
+
+def mapped_address(host):
+    """Device address of a pinned host tensor (pinned memory is mapped): a launch loads or
+    stores there over the host link."""
+    dev = c_void_p()
+    call('xa_host_device_pointer', c_void_p(host.data_ptr()), ctypes.byref(dev))
+    return dev.value
+
+
+def mapped_pinned(shape, dtype):
+    """(zero-filled pinned host tensor, its device address)."""
+    host = torch.zeros(shape, dtype=dtype).pin_memory()
+    return host, mapped_address(host)

@@ -531,7 +531,7 @@ class BaseAgent(ABC):
             for d, h in segs:
                 h.copy_(d, non_blocking=True)
             return
-        from xagents_amd._lib import XaHostCopyArgs, call, stream
+        from xagents_amd._lib import XaHostCopyArgs, call, mapped_address, stream
         import ctypes
         key = tuple((d.data_ptr(), h.data_ptr(), d.numel() * d.element_size()) for d, h in segs)
         cache = self.__dict__.setdefault('_host_copy_args', {})
@@ -541,9 +541,7 @@ class BaseAgent(ABC):
             a.n_segments = len(segs)
             for i, (d, h) in enumerate(segs):
                 assert d.is_contiguous() and h.is_contiguous() and h.is_pinned()
-                dev = ctypes.c_void_p()
-                call('xa_host_device_pointer', ctypes.c_void_p(h.data_ptr()), ctypes.byref(dev))
-                a.src[i], a.dst[i] = d.data_ptr(), dev.value
+                a.src[i], a.dst[i] = d.data_ptr(), mapped_address(h)
                 a.bytes[i] = d.numel() * d.element_size()
             cache[key] = a
         call('xa_copy_to_host', ctypes.byref(a), stream())
@@ -737,6 +735,36 @@ class OffPolicy(BaseAgent, ABC):
         if beta != self.per_beta:
             self.per_beta = beta
             self.per.set_beta(beta)
+
+    # ---- the sampled batch's slots: one learner-phase order, two slot sources ----------
+    # uniform replay draws them on the host (the reference's RNG streams) before the phase is
+    # enqueued; prioritized replay draws them in the phase's first launch. The phase itself is
+    # the same either way: gather from _phase_slots(), the TD head with _per_ptrs(), and
+    # per.update() behind it when there is a sampler.
+    def _draw_slots(self, stage=None):
+        """Host side, before the phase that gathers is enqueued. Uniform: sample_slots() into
+        `stage` (a SlotStage the gather reads in place) or, without one, uploaded into
+        replay.slots. Prioritized: nothing."""
+        if self.per is None:
+            slots = self.replay.sample_slots()
+            if stage is not None:
+                stage.put(slots)
+            else:
+                self.replay.upload_slots(slots)
+
+    def _phase_slots(self, stage=None):
+        """Inside the phase: the device address the gather reads its slots from (prioritized:
+        behind the xa_per_sample launch that draws them)."""
+        if self.per is not None:
+            return self.per.sample().data_ptr()
+        return stage.address(0) if stage is not None else self.replay.slots.data_ptr()
+
+    def _per_ptrs(self):
+        """(importance weights in, |TD error| out) of the weighted TD heads; null without a
+        sampler, which gives the plain head's bytes."""
+        if self.per is None:
+            return None, None
+        return self.per.weights.data_ptr(), self.per.td_abs.data_ptr()
 
     # ---- device env stepping + replay append (step_envs(store_in_buffers=True)) ----
     _STATS_ROWS = 64

@@ -16,11 +16,12 @@ import numpy as np
 import torch
 
 from xagents_amd import kernels
-from xagents_amd._lib import call, stream
+from xagents_amd._lib import call, mapped_pinned, stream
 from xagents_amd.base import OffPolicy
 from xagents_amd.envs import Box
 from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor
+from xagents_amd.replay import SlotStage
 
 
 class DDPG(OffPolicy):
@@ -219,8 +220,8 @@ class DDPG(OffPolicy):
         self._adam(self.actor, self.g_actor, mean=True)
 
     def concat_buffer_samples(self):
-        slots = self.replay.upload_slots(self.replay.sample_slots())
-        self.replay.gather(slots, self.s, self.a, self.r, self.d, self.s2)
+        self._draw_slots()
+        self.replay.gather(self._phase_slots(), self.s, self.a, self.r, self.d, self.s2)
         return [self.s, self.a, self.r, self.d, self.s2]
 
     def update_weights(self, gradient_steps):
@@ -230,21 +231,23 @@ class DDPG(OffPolicy):
         models are the 3-layer .cfg MLPs and the run is one process; otherwise the layer
         executor's ~40-90 launches, captured once per phase and replayed as hipGraphs."""
         fused = self._fused_args()
+        stage = self._fused_stage() if fused is not None and not self.distributed else None
         for gradient_step in range(int(gradient_steps)):
             policy = gradient_step % self.policy_delay == 0
-            if fused is not None and not self.distributed and self._staged_slots_ok():
+            if stage is not None:
                 # the launch reads the sampled slots from one of two mapped pinned buffers
-                # (no upload copy); one captured graph per (phase, buffer)
-                i = self._stage_fused_slots(self.replay.sample_slots())
-                fused.slots = self._fslots['dev'][i]
+                # (each workgroup once, over the host link, into its LDS slot table: no upload
+                # copy); one captured graph per (phase, buffer)
+                i = stage.put(self.replay.sample_slots())
+                fused.slots = stage.address(i)
                 if self._fused_graph():
                     self._run_phase(('fused_actor' if policy else 'fused') + f'@{i}',
                                     lambda p=policy: self._fused_step(p))
                 else:
                     self._fused_step(policy)
-                self._fslots['ev'][i].record()
+                stage.consumed(i)
                 continue
-            self.replay.upload_slots(self.replay.sample_slots())
+            self._draw_slots()
             if fused is not None and self.distributed:
                 self._fused_dp_step(policy)
                 continue
@@ -258,13 +261,15 @@ class DDPG(OffPolicy):
                 self._run_phase('actor', self._actor_phase)
 
     # ---- the fused gradient step (xa_td3_update) -------------------------------------
-    def _staged_slots_ok(self):
-        """(XA_TD3_STAGED_SLOTS=0: the upload copy into the device slot buffer instead)"""
-        if '_sslots' not in self.__dict__:
+    def _fused_stage(self):
+        """The two rotating SlotStage buffers of the fused step, or None (XA_TD3_STAGED_SLOTS=0:
+        the upload copy into the device slot buffer instead)."""
+        if '_fstage' not in self.__dict__:
             import os
-            self._sslots = os.environ.get('XA_TD3_STAGED_SLOTS', '1') != '0' and \
+            on = os.environ.get('XA_TD3_STAGED_SLOTS', '1') != '0' and \
                 torch.device(self.device).type == 'cuda'
-        return self._sslots
+            self._fstage = SlotStage(self.batch_size, 2) if on else None
+        return self._fstage
 
     def _fused_graph(self):
         """Launch the one-kernel gradient step directly (default) or replay it from a captured
@@ -275,31 +280,6 @@ class DDPG(OffPolicy):
             import os
             self._fgraph = os.environ.get('XA_TD3_GRAPH', '0') == '1'
         return self._fgraph
-
-    def _stage_fused_slots(self, slots):
-        """The gradient step's sample slots into one of two mapped pinned buffers, which the
-        fused launch reads over the host link (each workgroup once, into its LDS slot
-        table), replacing the host -> device copy launch. Alternates buffers; the launch
-        that read this buffer two gradient steps ago must have finished (its event).
-        Returns the buffer index."""
-        st = self.__dict__.get('_fslots')
-        if st is None:
-            bufs, devs = [], []
-            for _ in range(2):
-                t = torch.zeros(len(slots), dtype=torch.int64).pin_memory()
-                dp = ctypes.c_void_p()
-                call('xa_host_device_pointer', ctypes.c_void_p(t.data_ptr()), ctypes.byref(dp))
-                bufs.append(t)
-                devs.append(dp.value)
-            st = self._fslots = {'buf': bufs, 'dev': devs, 'i': 0,
-                                 'ev': [torch.cuda.Event(), torch.cuda.Event()], 'used': [False] * 2}
-        i = st['i']
-        if st['used'][i]:
-            st['ev'][i].synchronize()
-        st['buf'][i].numpy()[:] = slots
-        st['used'][i] = True
-        st['i'] = i ^ 1
-        return i
 
     def _shared_blocks(self):
         """Grid of the persistent TD3 launches (0 = the kernel's default, one workgroup per
@@ -487,7 +467,7 @@ class DDPG(OffPolicy):
         return f
 
     def _critic_phase(self):
-        self.replay.gather(self.replay.slots, self.s, self.a, self.r, self.d, self.s2)
+        self.replay.gather(self._phase_slots(), self.s, self.a, self.r, self.d, self.s2)
         self.update_critic_weights()
 
     def _actor_phase(self):
@@ -513,10 +493,8 @@ class DDPG(OffPolicy):
         self._stage_host = os.environ.get('XA_TD3_HOST_STAGE', '1') != '0' and \
             torch.device(self.device).type == 'cuda'
         if self._stage_host:
-            self._stage = torch.zeros(2, self.n_envs, dtype=torch.float32).pin_memory()
-            dp = ctypes.c_void_p()
-            call('xa_host_device_pointer', ctypes.c_void_p(self._stage.data_ptr()), ctypes.byref(dp))
-            self._stage_ptrs = (dp.value, dp.value + 4 * self.n_envs)
+            self._stage, dp = mapped_pinned((2, self.n_envs), torch.float32)
+            self._stage_ptrs = (dp, dp + 4 * self.n_envs)
             self._stage_ev = torch.cuda.Event()
             self._stage_rows = 0
         else:

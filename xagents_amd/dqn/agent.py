@@ -15,12 +15,7 @@ train_step (dqn/agent.py:182-197), all on device except the reference's host RNG
                          gradient round trip), the other layers' via xa_clip_adam
 at_step_end: hard target copy when steps % target_sync_steps == 0 (xa_polyak, tau 1).
 
-prioritized=True (xagents_amd/per.py; NOT a parity mode: the reference samples uniformly, and
-its RNG streams are not consumed by the draw): the learner phase becomes
-    xa_per_sample (slots, weights on device) -> xa_ring_gather from the device slots ->
-    forward -> xa_dqn_td_grad_w (dq and loss times the weight, |TD error| out) ->
-    xa_per_update -> backward -> Adam
-with no host slot draw and no staging; the Q head's TD step takes the separate launch.
+prioritized=True (per.py; NOT a parity mode): the sampler is the phase's slot source (base.py).
 """
 import os
 
@@ -33,6 +28,7 @@ from xagents_amd.base import OffPolicy
 from xagents_amd.envs import Discrete
 from xagents_amd.graph_phase import CapturedPhase
 from xagents_amd.layers import LayerExecutor, adam_apply
+from xagents_amd.replay import SlotStage
 
 
 class DQN(OffPolicy):
@@ -189,13 +185,10 @@ class DQN(OffPolicy):
         """One sampled batch gathered from the device rings in the reference's index
         order: [states, actions, rewards, dones, new_states] (base.py:344-368); prioritized:
         the sampler's draw (its weights at self.per.weights)."""
-        if self.per is not None:
-            slots = self.per.sample()
-        else:
-            slots = self.replay.upload_slots(self.replay.sample_slots())
+        self._draw_slots()
         B = self.batch_size
-        self.replay.gather(slots, self.xb[:B], self.b_act, self.b_rew, self.b_done,
-                           self.xb[B:])
+        self.replay.gather(self._phase_slots(), self.xb[:B], self.b_act, self.b_rew,
+                           self.b_done, self.xb[B:])
         return [self.xb[:B], self.b_act, self.b_rew, self.b_done, self.xb[B:]]
 
     def _td_grad(self):
@@ -209,20 +202,12 @@ class DQN(OffPolicy):
             return
         q_next_t = self.ex_target.forward(self.xb[B:])[0]
         q_next_o = q_all[B:].data_ptr() if self.double else None
-        if self.per is not None:
-            # the fused head carries no weights: the separate launch, weighted, |TD error| out
-            call('xa_dqn_td_grad_w', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
-                 self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
-                 self.n_actions, kernels._f32(self.gamma),
-                 kernels._f32(self.huber_delta or 0.0), self.dq.data_ptr(),
-                 self.td_loss.data_ptr(), self.model.optimizer.iterations.data_ptr(),
-                 self.per.weights.data_ptr(), self.per.td_abs.data_ptr(), stream())
-            return
-        call('xa_dqn_td_grad', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
+        # (the fused head carries no weights; null weights: xa_dqn_td_grad's bytes)
+        call('xa_dqn_td_grad_w', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
              self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
              self.n_actions, kernels._f32(self.gamma), kernels._f32(self.huber_delta or 0.0),
              self.dq.data_ptr(), self.td_loss.data_ptr(),
-             self.model.optimizer.iterations.data_ptr(), stream())
+             self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), stream())
 
     # the raw gradient of the dense layers whose Adam step runs inside their weight-gradient
     # GEMM is written to self.grad only on request (the raw-gradient parity tests)
@@ -340,26 +325,22 @@ class DQN(OffPolicy):
         self.get_actions()
         self._env_step(self.actions)
         self.steps += self.n_envs
-        if self.per is not None:
-            self._run_learn()  # the draw is the phase's first launch: nothing to stage
-            return
-        # host index draw in the reference's order, then the device learner phase (its
-        # gather reads the staged slots from mapped pinned memory: no upload launch;
-        # XA_PINNED_SLOTS=0: the upload copy)
-        if self._pinned_slots():
-            self.replay.stage_slots(self.replay.sample_slots())
-            self._run_learn()
-            if self.replay._stage_open:  # (graph replay: no event inside the capture)
-                self.replay.stage_consumed()
-        else:
-            self.replay.upload_slots(self.replay.sample_slots())
-            self._run_learn()
+        # host index draw in the reference's order, then the device learner phase
+        stage = self._gather_stage()
+        self._draw_slots(stage)
+        self._run_learn()
+        if stage is not None:  # (unless the phase did: a graph replay records no event)
+            stage.consumed(0)
 
-    def _pinned_slots(self):
-        if '_pslots' not in self.__dict__:
-            self._pslots = os.environ.get('XA_PINNED_SLOTS', '1') != '0' and \
+    def _gather_stage(self):
+        """The one mapped pinned buffer the learner phase's gather reads the host-drawn slots
+        from (no upload launch; one fixed address, one captured learner graph), or None: the
+        sampler draws them, or XA_PINNED_SLOTS=0 (the upload copy into replay.slots)."""
+        if '_gstage' not in self.__dict__:
+            on = self.per is None and os.environ.get('XA_PINNED_SLOTS', '1') != '0' and \
                 torch.device(self.device).type == 'cuda'
-        return self._pslots
+            self._gstage = SlotStage(self.batch_size, 1) if on else None
+        return self._gstage
 
     def _stage_early(self):
         """Record the staged slots' completion event right behind the gather (default;
@@ -371,24 +352,18 @@ class DQN(OffPolicy):
     def _learn_phase(self):
         """gather the sampled batch -> TD gradient -> CNN backward -> Keras Adam."""
         B = self.batch_size
-        r = self.replay
-        if self.per is not None:
-            # sample -> gather from the device slots -> weighted TD -> priorities -> update
-            r.gather(self.per.sample(), self.xb[:B], self.b_act, self.b_rew, self.b_done,
-                     self.xb[B:])
-            self._td_grad()
-            self.per.update()
-            self._apply()
-            return
-        src = (r.stage_ptr(), r.slots.numel()) if self._pinned_slots() else r.slots
-        r.gather(src, self.xb[:B], self.b_act, self.b_rew, self.b_done, self.xb[B:])
-        if self._pinned_slots() and self._stage_early() and \
+        stage = self._gather_stage()
+        self.replay.gather(self._phase_slots(stage), self.xb[:B], self.b_act, self.b_rew,
+                           self.b_done, self.xb[B:])
+        if stage is not None and self._stage_early() and \
                 not torch.cuda.is_current_stream_capturing():
-            # the gather is the staged slots' only reader: the next step's stage_slots waits
-            # for it alone, not for the whole learner phase, so the host enqueues the next
-            # acting launches while this backward runs (no idle gap between steps)
-            r.stage_consumed()
+            # the gather is the staged slots' only reader: the next step's put waits for it
+            # alone, not for the whole learner phase, so the host enqueues the next acting
+            # launches while this backward runs (no idle gap between steps)
+            stage.consumed(0)
         self._td_grad()
+        if self.per is not None:
+            self.per.update()
         self._apply()
 
     def _run_learn(self):

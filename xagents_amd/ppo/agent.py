@@ -254,8 +254,6 @@ class PPO(A2C):
         into XA_PPO_STATS_SLOTS mapped pinned host slots chosen by the launch number -- no
         xa_copy_to_host launch per train step, and several train steps per graph replay. Off with XA_STATS_IN_UPDATE=0 or the opt-in
         side-stream copy."""
-        import ctypes
-        from xagents_amd._lib import call
         u.stats_words = 0
         self._stats_fused = False
         if os.environ.get('XA_STATS_IN_UPDATE', '1') == '0' or \
@@ -264,18 +262,14 @@ class PPO(A2C):
         nd, sd, oe, se, os_ = self._stats_views
         nw = os_ + 1  # through the status word
         if getattr(self, '_fused_host', None) is None or self._fused_host[0].numel() != nw + 1:
-            self._fused_host = [torch.zeros(nw + 1, dtype=torch.float32).pin_memory()
-                                for _ in range(_lib.XA_PPO_STATS_SLOTS)]
+            self._fused_host, self._fused_dev = zip(*(
+                _lib.mapped_pinned(nw + 1, torch.float32)
+                for _ in range(_lib.XA_PPO_STATS_SLOTS)))
             self._fused_done = [h[:nd].view(sd) for h in self._fused_host]
             self._fused_epret = [h[oe:oe + se[0] * se[1]].view(se) for h in self._fused_host]
             self._fused_host_status = [h[os_:os_ + 1].view(torch.int32)
                                        for h in self._fused_host]
             self._fused_gen = [h[nw:nw + 1].view(torch.int32) for h in self._fused_host]
-            self._fused_dev = []
-            for h in self._fused_host:
-                dp = ctypes.c_void_p()
-                call('xa_host_device_pointer', ctypes.c_void_p(h.data_ptr()), ctypes.byref(dp))
-                self._fused_dev.append(dp.value)
         u.stats_src = self._stats_pack.data_ptr()
         for i, dp in enumerate(self._fused_dev):
             u.stats_dst[i] = dp

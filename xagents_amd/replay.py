@@ -23,7 +23,8 @@ import random
 import numpy as np
 import torch
 
-from xagents_amd._lib import XA_RING_DEQUE, XA_RING_RB2, XaGatherArgs, call, stream
+from xagents_amd._lib import (XA_RING_DEQUE, XA_RING_RB2, XaGatherArgs, call, mapped_pinned,
+                              stream)
 from xagents_amd.utils.buffers import ReplayBuffer1, ReplayBuffer2
 
 
@@ -97,6 +98,54 @@ def _fast_sampler():
     return lambda lengths, k: _sample_ranges(lengths, k, gb)
 
 
+class SlotStage:
+    """`depth` mapped pinned int64 buffers of `n_items` sampled slots, written by the host in
+    rotation and read by a launch over the host link (8 B per item) or by a host -> device
+    copy. A buffer's device address is fixed for its life, so a captured hipGraph may read it.
+
+    The host may overwrite a buffer only after the last reader of its contents ran. put()
+    therefore waits, for the buffer it is about to write:
+    * never used: for nothing;
+    * its reader reported (consumed): for that reader's completion event;
+    * its reader never reported (the read was enqueued inside a capture, where no event is
+      recorded): for the whole current stream (safe, slower)."""
+
+    def __init__(self, n_items, depth):
+        bufs = [mapped_pinned(n_items, torch.int64) for _ in range(depth)]
+        self._host = [h for h, _ in bufs]
+        self._dev = [d for _, d in bufs]
+        self._np = [h.numpy() for h in self._host]
+        self._ev = [torch.cuda.Event() for _ in range(depth)]  # (complete until recorded)
+        self._open = [False] * depth  # written, its reader has not reported
+        self._next = 0
+
+    def put(self, slots):
+        """The next batch's slots into the next buffer of the rotation; returns its index."""
+        i = self._next
+        if self._open[i]:
+            torch.cuda.current_stream().synchronize()
+        else:
+            self._ev[i].synchronize()
+        self._np[i][:] = slots
+        self._open[i] = True
+        self._next = (i + 1) % len(self._np)
+        return i
+
+    def address(self, i):
+        return self._dev[i]
+
+    def host(self, i):
+        return self._host[i]
+
+    def consumed(self, i):
+        """Call right behind the launch, graph replay or copy that read buffer i: records its
+        completion event on the current stream. Once per put: the first report stands (a
+        phase that reported behind its gather is not reported again behind its last launch)."""
+        if self._open[i]:
+            self._ev[i].record()
+            self._open[i] = False
+
+
 class DeviceReplay:
     def __init__(self, buffers, obs_shape, obs_dtype, act_shape, act_dtype, device):
         b0 = buffers[0]
@@ -125,11 +174,8 @@ class DeviceReplay:
         self.host_count = np.zeros(n, np.int64)
         self.obs_bytes = self.states[0, 0].numel() * self.states.element_size()
         self.act_bytes = max(self.actions[0, 0].numel(), 1) * self.actions.element_size()
-        self._pinned = [torch.empty(n * self.k, dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._pin_ev = [None, None]
-        self._pin_slot = 0
         self.slots = torch.zeros(n * self.k, dtype=torch.int64, device=device)
-        self._stage = None  # the staged (mapped pinned) slots, allocated on first use
+        self._upload = None  # upload_slots' copy sources (a SlotStage), allocated on first use
 
     # ---- append (device) + host mirror -----------------------------------------
     def fill_step_args(self, a, actions):
@@ -183,60 +229,20 @@ class DeviceReplay:
         return out
 
     def upload_slots(self, slots):
-        s = self._pin_slot
-        if self._pin_ev[s] is not None:
-            self._pin_ev[s].synchronize()
-        self._pinned[s].numpy()[:] = slots
-        self.slots.copy_(self._pinned[s], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._pin_ev[s] = ev
-        self._pin_slot ^= 1
+        """Host slots into self.slots: one host -> device copy from a rotating stage buffer."""
+        if self._upload is None:
+            self._upload = SlotStage(self.n * self.k, 2)
+        st = self._upload
+        i = st.put(slots)
+        self.slots.copy_(st.host(i), non_blocking=True)
+        st.consumed(i)
         return self.slots
-
-    # ---- staged slots: the consuming launch reads them from mapped pinned memory ------
-    def stage_ptr(self):
-        """Device address of the mapped pinned buffer the staged slots live in (fixed for
-        the buffer's life, so a captured hipGraph may read it)."""
-        if self._stage is None:
-            from xagents_amd._lib import call as _call
-            self._stage = torch.zeros(self.n * self.k, dtype=torch.int64).pin_memory()
-            dp = ctypes.c_void_p()
-            _call('xa_host_device_pointer', ctypes.c_void_p(self._stage.data_ptr()),
-                  ctypes.byref(dp))
-            self._stage_dev = dp.value
-            self._stage_ev = torch.cuda.Event()
-            self._stage_open = False
-        return self._stage_dev
-
-    def stage_slots(self, slots):
-        """The next batch's slots into the staged buffer (no upload copy: the gather reads
-        them over the host link, 8 B per sampled item). The previous batch's consumer must
-        have run: its completion event (stage_consumed) is waited for first; without one the
-        whole stream is (safe, slower)."""
-        self.stage_ptr()
-        if self._stage_open:
-            torch.cuda.current_stream().synchronize()
-        else:
-            self._stage_ev.synchronize()
-        self._stage.numpy()[:] = slots
-        self._stage_open = True
-        return self._stage_dev
-
-    def stage_consumed(self):
-        """Call right after enqueueing the launch (or graph replay) that read the staged
-        slots."""
-        self._stage_ev.record()
-        self._stage_open = False
 
     def gather(self, slots, states, actions, rewards, dones, new_states):
         """The five fields of one sampled batch in one xa_ring_gather_fields launch (the
-        argument block is built once per destination set and reused). slots: a device
-        int64 tensor, or an (address, count) pair (the staged slots)."""
-        if isinstance(slots, tuple):
-            sp, sn = slots
-        else:
-            sp, sn = slots.data_ptr(), slots.numel()
+        argument block is built once per destination set and reused). slots: the device
+        address of n * k int64 slots (self.slots', a SlotStage buffer's, the sampler's)."""
+        sp, sn = slots, self.n * self.k
         key = (sp, sn, states.data_ptr(), actions.data_ptr(),
                rewards.data_ptr(), dones.data_ptr(), new_states.data_ptr())
         if getattr(self, '_gkey', None) != key:

@@ -13,10 +13,7 @@ alpha = exp(log_alpha) is read on device by every launch; the temperature step c
 every launch of a gradient step saw the same alpha. There is no target actor and no fused
 single-launch step.
 
-prioritized=True (xagents_amd/per.py; not a parity mode, the host RNG streams are not consumed
-by the draw): the critic phase starts with xa_per_sample instead of the host slot draw, gathers
-from the device slots, takes xa_sac_td_grad_w (dv times the weight, the twins' mean |TD error|
-out) and runs xa_per_update right behind it; the actor phase is unchanged.
+prioritized=True (per.py; not a parity mode): the sampler is the critic phase's slot source.
 """
 import numpy as np
 import torch
@@ -172,17 +169,14 @@ class SAC(TD3):
         self._concat(self.s, self.a, self.sa)
         v1 = self.ex_critic.forward(self.sa)[0]
         v2 = self.ex_critic2.forward(self.sa)[0]
-        td = (v1.data_ptr(), v2.data_ptr(), tv1.data_ptr(), tv2.data_ptr(),
-              self.logp_next.data_ptr(), self.log_alpha.data_ptr(), self.r.data_ptr(),
-              self.d.data_ptr(), self.batch_size, kernels._f32(self.gamma),
-              kernels._f32(self.huber_delta or 0.0), self.dv1.data_ptr(), self.dv2.data_ptr(),
-              self.critic_loss.data_ptr())
+        # (null weights: xa_sac_td_grad's bytes)
+        call('xa_sac_td_grad_w', v1.data_ptr(), v2.data_ptr(), tv1.data_ptr(), tv2.data_ptr(),
+             self.logp_next.data_ptr(), self.log_alpha.data_ptr(), self.r.data_ptr(),
+             self.d.data_ptr(), self.batch_size, kernels._f32(self.gamma),
+             kernels._f32(self.huber_delta or 0.0), self.dv1.data_ptr(), self.dv2.data_ptr(),
+             self.critic_loss.data_ptr(), *self._per_ptrs(), stream())
         if self.per is not None:
-            call('xa_sac_td_grad_w', *td, self.per.weights.data_ptr(),
-                 self.per.td_abs.data_ptr(), stream())
             self.per.update()
-        else:
-            call('xa_sac_td_grad', *td, stream())
         self.ex_critic.backward([self.dv1], self.g_critic)
         self.ex_critic2.backward([self.dv2], self.g_critic2)
         self._adam(self.critic1, self.g_critic)
@@ -211,26 +205,6 @@ class SAC(TD3):
     def update_temperature(self):
         """One Keras Adam step on log_alpha from xa_sac_actor_seed's gradient."""
         self._adam(self.temperature, self.g_log_alpha, mean=True)
-
-    # ---- prioritized replay: the draw opens the critic phase -------------------------
-    def concat_buffer_samples(self):
-        if self.per is None:
-            return super().concat_buffer_samples()
-        self.replay.gather(self.per.sample(), self.s, self.a, self.r, self.d, self.s2)
-        return [self.s, self.a, self.r, self.d, self.s2]
-
-    def _critic_phase(self):
-        if self.per is None:
-            return super()._critic_phase()
-        self.concat_buffer_samples()
-        self.update_critic_weights()
-
-    def update_weights(self, gradient_steps):
-        if self.per is None:
-            return super().update_weights(gradient_steps)
-        for _ in range(int(gradient_steps)):  # no host slot draw, nothing staged
-            self._run_phase('critic', self._critic_phase)
-            self._run_phase('actor', self._actor_phase)
 
     def at_step_start(self):
         self._per_anneal()
