@@ -630,6 +630,37 @@ int xa_dqn_td_grad_w(const float* q, const float* q_next_target, const float* q_
                      int n_actions, float gamma, float huber_delta, float* dq, float* loss,
                      int* adam_step, const float* is_weights, float* td_abs, void* stream);
 
+/* Quantile-regression DQN (Dabney et al., https://arxiv.org/abs/1710.10044; csrc/qr.hip,
+ * csrc/qr_terms.hpp states the arithmetic). A network output row theta is [n_actions]
+ * [n_quantiles], action-major: output a N + i is quantile i of action a, at the midpoint
+ * tau_hat_i = (2 i + 1) / (2 N) (Lemma 2). Q[a] = (sum_i theta[a][i]) / N. One wave per row;
+ * 1 <= n_quantiles <= 256, any n_actions >= 1, anything else is an error.
+ *
+ * xa_qr_act: actions[r] = first argmax_a Q[a] of row r of theta [n][A N], or
+ * random_actions[r] when use_random (xa_dqn_act's rule; theta and q_mean are then not
+ * touched). q_mean [n][A] (optional) receives the mean Q values.
+ *
+ * xa_qr_td_grad (Algorithm 1): a* = argmax_a Q[a] of theta_next_target's row (of
+ * theta_next_online's when it is not NULL: double Q), target quantiles
+ * y_j = theta_next_target[b][a*][j] gamma + r, y_j = r where done. With
+ * u_ij = y_j - theta[b][a_b][i], L_kappa the Huber loss (Eq. 9) and the quantile Huber loss
+ * rho_ij = |tau_hat_i - [u_ij < 0]| L_kappa(u_ij) / kappa (Eq. 10, normalised by kappa):
+ * loss[b] (optional) = sum_i (sum_j rho_ij) / N, and the gradient of the batch MEAN
+ * dtheta[b][a_b][i] = -((sum_j |tau_hat_i - [u_ij < 0]| clip(u_ij, +-kappa) / kappa) / N) / batch,
+ * 0 at every other action's outputs: the whole [batch][A N] array is written. huber_kappa
+ * must be > 0. adam_step (optional) is bumped by one in the same launch. Prioritized replay,
+ * both optional and both NULL the unweighted bytes: is_weights [batch] (in) multiplies
+ * dtheta's row and loss[b] by w_b, one f32 multiply after the unweighted value; td_abs
+ * [batch] (out) = |(sum_j y_j) / N - Q[a_b]|, the TD error of the means. */
+int xa_qr_act(const float* theta, int n, int n_actions, int n_quantiles,
+              const int* random_actions, int use_random, int* actions, float* q_mean,
+              void* stream);
+int xa_qr_td_grad(const float* theta, const float* theta_next_target,
+                  const float* theta_next_online, const int* actions, const float* rewards,
+                  const float* dones, int batch, int n_actions, int n_quantiles, float gamma,
+                  float huber_kappa, float* dtheta, float* loss, int* adam_step,
+                  const float* is_weights, float* td_abs, void* stream);
+
 /* The Q head (the last dense layer, N <= 8 actions: xa_gemm's row-dot shape) with DQN's
  * per-row step fused into the same launch. mode 0: actions[m] = first argmax of row m
  * (xa_dqn_act's greedy branch); mode 1: the head is the TARGET network's over s', and row b

@@ -513,6 +513,13 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
          c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    'xa_qr_act': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                          c_void_p]),
+    'xa_qr_td_grad': (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     'xa_ring_scatter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'xa_ring_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'xa_ring_gather_fields': (c_int, [c_void_p, c_void_p]),

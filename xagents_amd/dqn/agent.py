@@ -312,16 +312,29 @@ class DQN(OffPolicy):
         self.update_epsilon()
         self._per_anneal()
 
+    def _hooks_overridden(self, base):
+        """A subclass of `base` (the agent class whose device step this is) overrides one of
+        the reference's hooks: its train step composes them."""
+        hooks = ('get_targets', 'update_gradients', 'concat_buffer_samples', 'get_actions')
+        return any(getattr(type(self), h) is not getattr(base, h) for h in hooks)
+
+    def _composed_step(self):
+        """The train step through the hooks, each calling the library."""
+        actions = self.get_actions()
+        self._env_step(actions.to(torch.int32).contiguous())
+        self.steps += self.n_envs
+        batch = self.concat_buffer_samples()
+        self.update_gradients(batch[0], self.get_targets(*batch))
+
     def train_step(self):
         """dqn/agent.py:182-197"""
-        hooks = ('get_targets', 'update_gradients', 'concat_buffer_samples', 'get_actions')
-        if any(getattr(type(self), h) is not getattr(DQN, h) for h in hooks):
-            actions = self.get_actions()
-            self._env_step(actions.to(torch.int32).contiguous())
-            self.steps += self.n_envs
-            batch = self.concat_buffer_samples()
-            self.update_gradients(batch[0], self.get_targets(*batch))
-            return
+        if self._hooks_overridden(DQN):
+            self._composed_step()
+        else:
+            self._device_step()
+
+    def _device_step(self):
+        """The train step on the device path: act, step + append, then the learner phase."""
         self.get_actions()
         self._env_step(self.actions)
         self.steps += self.n_envs
