@@ -16,7 +16,9 @@ from collections import Counter
 
 HEAD = 'ppo_update_kernelILi4ELi2ELi16ELb0ELb1ELi3E'
 CLASSES = ['v_readlane', 'v_readfirstlane', 'v_writelane', 'v_accvgpr', 's_nop', 's_waitcnt',
-           's_load', 's_cbranch', 'v_cmp', 'buffer_store', 'buffer_load', 's_barrier']
+           's_load', 's_cbranch', 'v_cmp', 'buffer_store', 'buffer_load', 's_barrier', 'ds_',
+           'v_cndmask']
+DPP = '*_dpp'  # any VALU instruction with a DPP operand (counted by its mnemonic's suffix)
 
 
 def kernel_body(path, name):
@@ -122,6 +124,8 @@ def count(ins, bl, body):
             for k in CLASSES:
                 if mn.startswith(k):
                     c[k] += 1
+            if mn.endswith('_dpp'):
+                c[DPP] += 1
             c['instructions'] += 1
     return c
 
@@ -150,7 +154,7 @@ def main(path, name=HEAD):
         tot, slw = count(ins, bl, body), count(ins, bl, slow)
         print(f'\n  {kind}: {len(body)} blocks, {len(slow)} of them on poll slow paths')
         print(f'    {"class":<18}{"static":>8}{"slow-path blocks":>18}')
-        for k in ['instructions'] + CLASSES:
+        for k in ['instructions'] + CLASSES + [DPP]:
             print(f'    {k:<18}{tot[k]:>8}{slw[k]:>18}')
 
 

@@ -12,9 +12,13 @@
 //   2  Z2[s][i] = H1[s] W2[:, i]                 MFMA, B operand = the lane's own W2 column
 //      H2 = tanh(Z2 + b2) in registers;          (thread ownership below)
 //      head partials over the wave's 16 units    DPP row sums -> LDS            | barrier
+//                                                (TS = 16: one transposing row sum, every
+//                                                lane stores one (sample, head) total)
 //   3  logits / value (4 wave partials + b34), the clipped PPO loss and dL/dz per sample,
-//      each lane for its own samples (no broadcast; the loss terms and their tie rules
-//      are ac_loss.hpp's); dA2 = (dz W34^T)(1 - H2^2) in
+//      one sample per lane (the loss terms and their tie rules are ac_loss.hpp's); dz to
+//      the lanes of the MFMA layout through a wave-private LDS copy (TS = 32) or as a DPP
+//      row broadcast (TS = 16: lane row lq evaluates samples 4 lq .. 4 lq + 3 on its
+//      lanes 0..3); dA2 = (dz W34^T)(1 - H2^2) in
 //      registers and LDS; head / b2 gradients;
 //      dW2[:, i] += H1^T dA2                     MFMA, B operand = the lane's dA2   | barrier
 //   4  dH1[s][i] = dA2[s] W2[i, :]^T             MFMA (A: dA2 from LDS, B: W2 row i,
@@ -186,6 +190,78 @@ XA_DEV float xa_sum16(float v) {
   return v + XA_DPP_F(v, 0x140);  // row_mirror
 }
 
+// The tile's two in-wave hand-offs at TS = 16 (each a -D switch for A/B builds, on in the
+// tree; with both off the file compiles to the forms they replace; the 32-sample tile keeps
+// those in either case):
+//   XA_PT_TSUM    the head partials by one transposing row sum (xa_tsum16) instead of one
+//                 xa_sum16 per (sample, head)
+//   XA_PT_DZPERM  lane row lq evaluates the loss of the samples rotated by 4 lq, so dL/dz of
+//                 its four MFMA-layout samples is a row broadcast of its lanes 0..3 (DPP
+//                 operands of the multiply-adds) instead of a trip through the wave-private
+//                 sdz copy
+#ifndef XA_PT_TSUM
+#define XA_PT_TSUM 1
+#endif
+#ifndef XA_PT_DZPERM
+#define XA_PT_DZPERM 1
+#endif
+
+// Transposing sum over aligned 16-lane rows: N values per lane in, and at the end the lane
+// of row position li holds, in v[16 c], the row's total of value number 16 c + xa_tsum16_index(li)
+// (garbage where that number is >= N). Stage K pairs the values whose numbers differ in bit
+// K: a lane keeps the one whose bit K equals bit K of its index, hands the other to its
+// partner and adds what the partner hands over, so the payload halves with every stage. The
+// partners are xa_sum16's (quad_perm 1, quad_perm 2, row_half_mirror, row_mirror), and the
+// index map makes the two mirrors join lanes that hold the same numbers; every total is
+// therefore the same tree of the same operand pairs as xa_sum16's, the same bits.
+XA_DEV int xa_tsum16_index(int li) { return li ^ ((li & 4) ? 3 : 0) ^ ((li & 8) ? 4 : 0); }
+
+template <int K, int N, int NP>
+XA_DEV void xa_tsum16_stage(float (&v)[NP], int e) {
+  constexpr int CTRL = K == 0 ? 0xB1 : K == 1 ? 0x4E : K == 2 ? 0x141 : 0x140;
+  // the stage's bit as a value of its own: one compare per stage (left visible, the four
+  // stages' selects are merged into one chain of compares of e against every number)
+  int bit = e & (1 << K);
+  asm volatile("" : "+v"(bit));
+  const bool up = bit != 0;
+#pragma unroll
+  for (int j0 = 0; j0 < NP; j0 += 2 << K) {
+    const int j1 = j0 + (1 << K);
+    if (j0 < N && j1 < N) {
+      const float keep = up ? v[j1] : v[j0], send = up ? v[j0] : v[j1];
+      v[j0] = keep + XA_DPP_F(send, CTRL);
+    } else if (j0 < N) {  // no value with bit K set: the plain stage
+      v[j0] = v[j0] + XA_DPP_F(v[j0], CTRL);
+    }
+  }
+}
+
+// e = xa_tsum16_index of the lane's row position (taken as a parameter so the caller
+// chooses which copy of its lane index the four selects' compares are formed from)
+template <int N, int NP>
+XA_DEV void xa_tsum16(float (&v)[NP], int e) {
+  static_assert(NP % 16 == 0 && N <= NP && N > NP - 16, "NP = N rounded up to 16 lanes");
+  xa_tsum16_stage<0, N>(v, e);
+  xa_tsum16_stage<1, N>(v, e);
+  xa_tsum16_stage<2, N>(v, e);
+  xa_tsum16_stage<3, N>(v, e);
+}
+
+// lane r < 4 of the lane's own 16-lane row, on every lane of the row (row_newbcast; r is a
+// constant once the caller's loop is unrolled)
+// (every lane reads a lane that exists; bound_ctrl set, so the move needs no prior value of
+// its destination and can fold into the instruction that uses it)
+#define XA_ROW_LANE(v, r) \
+  __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + (r), 0xF, 0xF, true))
+XA_DEV float xa_row_lane(float v, int r) {
+  switch (r) {
+    case 0: return XA_ROW_LANE(v, 0);
+    case 1: return XA_ROW_LANE(v, 1);
+    case 2: return XA_ROW_LANE(v, 2);
+    default: return XA_ROW_LANE(v, 3);
+  }
+}
+
 // W2 row i = 16 w + li, columns 16 lq .. 16 lq + 15 (dH1's B operand), from the LDS copy
 template <int OBS, int A, int TS>
 XA_DEV void load_w2_rows(const PtLds<OBS, A, TS>& L, float (&w2r)[16]) {
@@ -325,25 +401,47 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
     }
   }
   stamp(51);
+  constexpr bool kTsum = XA_PT_TSUM && TS == 16, kDzPerm = XA_PT_DZPERM && TS == 16;
+  if constexpr (kTsum) {
+    // value number 4 a + r = H2[4 lq + r][i] W34[i][a]; the lane ends with the row's total
+    // of number 16 c + e and stores it (a lane whose number names no head: a finite sum
+    // into the row's padding columns, which nobody uses)
+    constexpr int NP = (4 * AH + 15) & ~15;
+    static_assert(NP / 4 <= PtLds<OBS, A, TS>::AHP, "the padding columns take the rest");
+    float p[NP];
 #pragma unroll
-  for (int mt = 0; mt < NT; ++mt)
+    for (int a = 0; a < AH; ++a)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < 4; ++r) p[4 * a + r] = h2[0][r] * w34[a];
+    xa_tsum16<4 * AH>(p, xa_tsum16_index(pli));
+    const int e = xa_tsum16_index(li);
 #pragma unroll
-      for (int a = 0; a < AH; ++a) {
-        const float p = xa_sum16(h2[mt][r] * w34[a]);
-        if (pli == 0) L.sZp[w][16 * mt + 4 * lq + r][a] = p;
-      }
+    for (int c = 0; c < NP / 16; ++c) L.sZp[w][4 * lq + (e & 3)][4 * c + (e >> 2)] = p[16 * c];
+  } else {
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int a = 0; a < AH; ++a) {
+          const float p = xa_sum16(h2[mt][r] * w34[a]);
+          if (pli == 0) L.sZp[w][16 * mt + 4 * lq + r][a] = p;
+        }
+  }
   __syncthreads();
   stamp(52);
   // ---- 3: loss + dL/dz, one sample per lane (lane li: sample 16 mt + li; the lane groups
-  // lq repeat it), handed to the lanes that need it through a wave-private LDS copy; dA2,
-  // head grads, dW2 ----
+  // lq repeat it), handed to the lanes that need it through a wave-private LDS copy or
+  // (kDzPerm) a row broadcast; dA2, head grads, dW2 ----
   constexpr int AHP = PtLds<OBS, A, TS>::AHP;
   const bool tally = pw == 0 && plq == 0;  // one lane per sample accumulates the sums
+  // kDzPerm: lane row lq evaluates the samples rotated by 4 lq, so its lanes 0..3 hold the
+  // four samples 4 lq + r of the row's MFMA layout and dz is a row broadcast of lane r (row
+  // 0, which holds the tally lanes, keeps sample li on lane li)
+  [[maybe_unused]] float dzl[AH];
 #pragma unroll
   for (int mt = 0; mt < NT; ++mt) {
-    const int s = 16 * mt + li;
+    const int s = kDzPerm ? ((li + 4 * lq) & 15) : 16 * mt + li;
     float z[AHP];
 #pragma unroll
     for (int a4 = 0; a4 < AHP; a4 += 4) {
@@ -403,7 +501,10 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
         for (int a = 0; a < AH; ++a) acc.gb34[a] += dz[a];
       }
     }
-    if (plq == 0) {
+    if constexpr (kDzPerm) {
+#pragma unroll
+      for (int a = 0; a < AH; ++a) dzl[a] = dz[a];
+    } else if (plq == 0) {
 #pragma unroll
       for (int a4 = 0; a4 < AHP; a4 += 4)
         *reinterpret_cast<float4*>(&L.sdz[w][s][a4]) = make_float4(dz[a4], dz[a4 + 1], dz[a4 + 2], dz[a4 + 3]);
@@ -411,7 +512,7 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
   }
   // the wave's own LDS writes are done before its reads (in-order LDS queue); keep the
   // compiler from moving the reads above them
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  if constexpr (!kDzPerm) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   float da2[NT][4];
 #pragma unroll
   for (int mt = 0; mt < NT; ++mt) {
@@ -419,10 +520,17 @@ XA_DEV void pt_tile(PtLds<OBS, A, TS>& L, PtAcc<OBS, A>& acc, const LossCfg& cfg
     for (int r = 0; r < 4; ++r) {
       const int s = 16 * mt + 4 * lq + r;
       float dz[AHP];
+      if constexpr (kDzPerm) {
+        // sample 4 lq + r was evaluated on lane r of this lane row (all 64 lanes are on
+        // here: the loss branch has rejoined)
 #pragma unroll
-      for (int a4 = 0; a4 < AHP; a4 += 4) {
-        const float4 t = *reinterpret_cast<const float4*>(&L.sdz[w][s][a4]);
-        dz[a4] = t.x; dz[a4 + 1] = t.y; dz[a4 + 2] = t.z; dz[a4 + 3] = t.w;
+        for (int a = 0; a < AH; ++a) dz[a] = xa_row_lane(dzl[a], r);
+      } else {
+#pragma unroll
+        for (int a4 = 0; a4 < AHP; a4 += 4) {
+          const float4 t = *reinterpret_cast<const float4*>(&L.sdz[w][s][a4]);
+          dz[a4] = t.x; dz[a4 + 1] = t.y; dz[a4 + 2] = t.z; dz[a4 + 3] = t.w;
+        }
       }
       // dA2 = (dz W34^T) (1 - H2^2), this lane's unit j = i
       float dh = 0.0f;
