@@ -379,6 +379,138 @@ def test_ctypes_structs_match_the_c_abi(tmp_path):
             assert got[(s.__name__, f[0])] == getattr(s, f[0]).offset, (s.__name__, f[0])
 
 
+_SMALL_HEADER = '''\
+/* a block comment with ; { } ( and a prototype: int xa_not_this(int x);
+ * typedef struct XaNotThis { int a; } XaNotThis; */
+#ifndef SMALL_H
+#define SMALL_H
+#include <stddef.h>
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define XA_SLOTS 3 /* } trailing ; comment ( */
+#define XA_MASK 0x10 // a line comment; with { and (
+typedef struct XaFoo {
+  int n, m;
+  const float* x; /* [n] ; */
+  float *p, *q;
+  uint64_t seed;
+} XaFoo;
+typedef struct XaBar {
+  XaFoo foo;          // nested {
+  XaFoo two, more;
+  void* blocks[XA_SLOTS];
+  int64_t bytes[XA_SLOTS];
+  XaFoo foos[XA_SLOTS];
+  unsigned* arrivals;
+  size_t ws_bytes;
+  double scale;
+  short s; uint8_t b; uint32_t w; unsigned u;
+} XaBar;
+const char* xa_name(void);
+size_t xa_bytes(size_t n, int world);
+int xa_run(const XaFoo* foo, XaBar* bar,
+           void** out, const void* handle /* 64 bytes; ( */,
+           const int64_t* slots, double d, float f, int64_t k, uint64_t seed, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+'''
+
+
+def test_header_reader_on_a_small_header():
+    """The reader behind _lib (xagents_amd/_header.py) on a header that has every shape the
+    real one uses: the exact constants, fields and signatures, and an error that names the
+    offending text for whatever it does not know."""
+    import ctypes
+    from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_short, c_size_t,
+                        c_uint, c_uint8, c_uint32, c_uint64, c_void_p)
+    from xagents_amd._header import HeaderError, read_header
+    h = read_header(_SMALL_HEADER)
+    assert h.constants == {'XA_SLOTS': 3, 'XA_MASK': 16}
+    assert list(h.structs) == ['XaFoo', 'XaBar']
+    foo, bar = h.structs['XaFoo'], h.structs['XaBar']
+    assert issubclass(foo, ctypes.Structure) and foo.__name__ == 'XaFoo'
+    assert foo._fields_ == [('n', c_int), ('m', c_int), ('x', c_void_p), ('p', c_void_p),
+                            ('q', c_void_p), ('seed', c_uint64)]
+    # array types are cached by ctypes, so `T * n` is the very type the reader built
+    assert bar._fields_ == [
+        ('foo', foo), ('two', foo), ('more', foo), ('blocks', c_void_p * 3),
+        ('bytes', c_int64 * 3), ('foos', foo * 3), ('arrivals', c_void_p),
+        ('ws_bytes', c_size_t), ('scale', c_double), ('s', c_short), ('b', c_uint8),
+        ('w', c_uint32), ('u', c_uint)]
+    assert h.signatures == {
+        'xa_name': (c_char_p, []),
+        'xa_bytes': (c_size_t, [c_size_t, c_int]),
+        'xa_run': (c_int, [POINTER(foo), POINTER(bar), POINTER(c_void_p), c_void_p, c_void_p,
+                           c_double, c_float, c_int64, c_uint64, c_void_p]),
+    }
+
+    def broken(old, new):
+        assert old in _SMALL_HEADER
+        return _SMALL_HEADER.replace(old, new, 1)
+
+    for text, offending in [
+        (broken('uint64_t seed;', 'ulong seed;'), 'ulong'),                    # unknown type
+        (broken('int n, m;', 'long long n;'), 'long long n'),
+        (broken('XaFoo* foo', 'XaBaz* foo'), 'XaBaz'),
+        (broken('double d', 'long d'), 'long'),
+        (broken('const char* xa_name', 'char xa_name'), 'char xa_name'),      # return type
+        (broken('  int n, m;', '  XaBar later;\n  int n, m;'), 'XaBar later'),  # used before
+        (broken('XaBar* bar', 'XaLater* bar'), 'XaLater'),                     # its definition
+        (broken('blocks[XA_SLOTS]', 'blocks[XA_NONE]'), 'XA_NONE'),            # undefined bound
+        (broken('blocks[XA_SLOTS]', 'blocks[4]'), 'blocks[4]'),
+        (broken('double scale;', 'void (*done)(int rc);'), '(*done)(int rc)'),  # function pointer
+        (broken('XaBar* bar', 'XaBar bar'), 'XaBar'),                          # struct by value
+        (broken('void** out', 'int** out'), 'int**'),
+        (broken('#define XA_SLOTS 3', '#define XA_SLOTS (1 + 2)'), '(1 + 2)'),
+        (broken('#define XA_MASK 0x10', '#define OTHER 5'), 'OTHER 5'),
+        (broken('const char* xa_name(void);', 'extern int xa_errno;'), 'xa_errno'),
+        (broken('} XaFoo;', '} XaFu;'), 'XaFoo'),
+    ]:
+        with pytest.raises(HeaderError) as err:
+            read_header(text)
+        assert offending in str(err.value), (offending, str(err.value))
+    # the message carries the header line of the declaration
+    with pytest.raises(HeaderError, match=r'small\.h:16: .*ulong'):
+        read_header(broken('uint64_t seed;', 'ulong seed;'), 'small.h')
+
+
+def test_binding_is_the_header():
+    """_lib's constants, structs and signatures are the real header's: every prototype is
+    bound, every struct a prototype names is a class, every array field has its #define's
+    length, and _lib holds no value of its own."""
+    import ctypes
+    from xagents_amd import _lib
+    header = (ROOT / 'include' / 'xagents_hip.h').read_text()
+    declared = re.findall(r'^\s*(?:int|size_t|const char\*)\s+(xa_\w+)\(', header, re.M)
+    assert len(declared) == len(set(declared)) == len(_lib._SIGNATURES) >= 93
+    assert set(declared) == set(_lib._SIGNATURES)
+    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    for name in set(re.findall(r'\b(Xa\w+)\s*\*', plain)):
+        assert issubclass(getattr(_lib, name), ctypes.Structure), name
+    typedefs = re.findall(r'typedef struct (Xa\w+) \{(.*?)\} \1;', plain, re.S)
+    assert len(typedefs) >= 27
+    assert [name for name, _ in typedefs] == [k for k in vars(_lib) if k.startswith('Xa')]
+    arrays = [(name, field, const) for name, body in typedefs
+              for field, const in re.findall(r'(\w+)\[(\w+)\]', body)]
+    assert {field for _, field, _ in arrays} == {'dp_blocks', 'stats_dst', 'field', 'src', 'dst',
+                                                 'bytes', 'blocks'}
+    for name, field, const in arrays:
+        ctype = dict(getattr(_lib, name)._fields_)[field]
+        assert issubclass(ctype, ctypes.Array) and ctype._length_ == getattr(_lib, const) > 0
+    for const, value in re.findall(r'^#define (XA_\w+) (\d+)', header, re.M):
+        assert getattr(_lib, const) == int(value), const
+    assert _lib.XA_ABI_VERSION == _lib.load().xa_abi_version()
+    assert _lib.MLP_HIDDEN == _lib.XA_MLP_HIDDEN == 64
+    # struct-taking entry points are typed, xa_ring_gather_fields included
+    assert _lib._SIGNATURES['xa_ring_gather_fields'] == (
+        ctypes.c_int, [ctypes.POINTER(_lib.XaGatherArgs), ctypes.c_void_p])
+    assert _lib._SIGNATURES['xa_host_device_pointer'][1][1] is ctypes.POINTER(ctypes.c_void_p)
+
+
 def test_fused_td3_entry_points_validate_sizes():
     """xa_td3_update / xa_td3_act refuse shapes beyond their tiles with a message (checked
     before any device call, so this runs without a GPU), and size their workspaces on the
