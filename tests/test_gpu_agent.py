@@ -109,6 +109,49 @@ def test_replan_to_chain_keeps_episode_stats(device, monkeypatch):
     assert a.done_envs == b.done_envs
 
 
+@pytest.mark.parametrize('switches, n_envs, transport', [
+    ({}, 16, 'fused'),
+    ({'XA_STATS_IN_UPDATE': '0'}, 16, 'copy'),    # done, epret, status as segments
+    ({'XA_STATS_IN_UPDATE': '0'}, 256, 'copy'),   # the whole pack (>= 65536 floats)
+    ({'XA_STATS_SIDE_STREAM': '1'}, 16, 'side'),
+], ids=['fused', 'copy-segments', 'copy-packed', 'side'])
+def test_episode_stats_transports_fold_the_device_buffers(device, monkeypatch, switches, n_envs,
+                                                          transport):
+    """Each transport of EpisodeStats against the device buffers themselves: after every
+    train step b_done / b_epret are read back and folded with the pure function into a
+    reference sink; after the drain the agent's bookkeeping equals the sink's exactly.
+    (The replay env's episode ends are the record's: with t_rec = 256 and 128 steps per
+    rollout every env finishes episodes in every train step, whatever the policy does.)"""
+    from collections import deque
+    from types import SimpleNamespace
+    from xagents_amd.base import BaseAgent
+    from xagents_amd.episode_stats import StatsLayout, fold_rollout
+
+    for k, v in switches.items():
+        monkeypatch.setenv(k, v)
+    agent = make_agent(n_envs=n_envs, n_steps=128, seed=7, t_rec=256)
+    ref = SimpleNamespace(history_checkpoint=None, games=0, done_envs=0,
+                          total_rewards=deque(maxlen=agent.total_rewards.maxlen))
+    for _ in range(6):
+        agent.train_step()
+        torch.cuda.synchronize()
+        finished, ref.episode_rewards, ref.dones = fold_rollout(agent.b_done.cpu().numpy(),
+                                                                agent.b_epret.cpu().numpy())
+        BaseAgent._record_finished(ref, finished)
+    agent._drain_episode_stats()
+    st = agent.episode_stats
+    assert st.active is getattr(st, transport) and agent._stats_fused == (transport == 'fused')
+    if transport != 'fused':
+        assert (st.active.stream is not None) == (transport == 'side')
+        assert st.active.packed == (n_envs == 256) == \
+            (st.layout.words >= StatsLayout.PACKED_COPY_MIN)
+    assert agent.games == ref.games > 0
+    assert list(agent.total_rewards) == list(ref.total_rewards)
+    assert agent.done_envs == ref.done_envs
+    assert agent.dones == ref.dones
+    np.testing.assert_array_equal(agent.episode_rewards, ref.episode_rewards)
+
+
 def test_ppo_train_step_vs_oracle_pipeline(device):
     """One full train step: rollout buffers bit-exact vs the C oracle (same Philox
     stream), then 4 epochs x 4 minibatches against the float64 restatement of the

@@ -474,7 +474,7 @@ def test_pending_optimizer_step_in_ac_grad_prologue(device):
 
 @pytest.mark.parametrize('sizes', [(16 * 129, 16 * 128, 1), (256 * 129, 256 * 128), (1,), (3, 5)])
 def test_copy_to_host_segments_bit_exact(device, sizes):
-    """xa_copy_to_host (episode statistics, base.py _copy_to_host): every segment lands in
+    """xa_copy_to_host (episode statistics, episode_stats.py _Copy.launch): every segment lands in
     its pinned host buffer word for word (f32 bit patterns incl. NaN payloads, int32)."""
     import ctypes
     g = torch.Generator().manual_seed(len(sizes))

@@ -32,7 +32,7 @@ def main():
                 slow.append((name, round(d * 1e3, 2)))
             return r
         return w
-    for name in ('_fold_stats', '_sync_stats_copy', '_queue_episode_stats', '_maybe_check_peer'):
+    for name in ('_record_finished', '_sync_stats_copy', '_queue_episode_stats', '_maybe_check_peer'):
         setattr(agent, name, timed(name, getattr(agent, name)))
     gc.callbacks.append(lambda phase, info: slow.append(('gc', phase, info.get('generation'))))
     for _ in range(5):

@@ -45,7 +45,7 @@ def run_modes(agent, n):
             ev[i][2].record(stream)
             if mode == 'probe':
                 # the control words and the launch generation after each launch
-                agent._queue_episode_stats(agent.b_done, agent.b_epret)
+                agent._queue_episode_stats()
                 torch.cuda.synchronize()
                 w = agent.update_ws[:512].cpu().view(torch.int32).numpy()
                 print(f'  probe {i:2d}: ctl {w[:8].tolist()} xcnt {w[8:16].tolist()} gen {w[64]}'

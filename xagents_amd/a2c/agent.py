@@ -20,6 +20,7 @@ from xagents_amd._lib import (XA_RETURNS_GAE, XA_RETURNS_NONE, XA_RETURNS_NSTEP,
                               XaAcGradArgs, XaRolloutArgs, XaShuffle)
 from xagents_amd.base import OnPolicy
 from xagents_amd.envs import Discrete
+from xagents_amd.episode_stats import EpisodeStats, StatsLayout
 from xagents_amd.onpolicy_executor import ExecutorActorCritic
 
 
@@ -96,14 +97,8 @@ class A2C(ExecutorActorCritic, OnPolicy):
         self.b_rew = torch.zeros(N, T, **f32)
         # done flags, running episode returns and a device status word in ONE buffer, so
         # the per-step episode statistics leave the device in one D2H copy
-        al = lambda x: (x + 63) // 64 * 64  # noqa: E731  (256-B aligned views)
-        o_ep = al(N * (T + 1))
-        o_st = o_ep + al(N * T)
-        self._stats_pack = torch.zeros(o_st + 64, **f32)
-        self.b_done = self._stats_pack[:N * (T + 1)].view(N, T + 1)
-        self.b_epret = self._stats_pack[o_ep:o_ep + N * T].view(N, T)
-        self._stats_status = self._stats_pack[o_st:o_st + 1].view(torch.int32)
-        self._stats_views = (N * (T + 1), (N, T + 1), o_ep, (N, T), o_st)
+        st = self.episode_stats = EpisodeStats(self, layout=StatsLayout.of(N, T))
+        self.b_done, self.b_epret, self._stats_status = st.done, st.epret, st.status
         self.b_ret = torch.zeros(N, T, **f32)
         self.next_val = torch.zeros(N, **f32)
         self.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -291,7 +286,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
             torch.cuda._sleep(20_000_000)
             self._step_impl()
             self.steps += self.n_envs * self.n_steps
-            self._queue_episode_stats(self.b_done, self.b_epret)
+            self._queue_episode_stats()
             torch.cuda.synchronize()
             return {k: [a.elapsed_time(b) for a, b in v] for k, v in self._kernel_events.items()}
         finally:
@@ -390,7 +385,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
             self._executor_update()
             rec(2)
             self.steps += self.n_envs * self.n_steps
-            self._queue_episode_stats(self.b_done, self.b_epret)
+            self._queue_episode_stats()
             return
         self._sync_stats_copy()
         if self._rollout_ev is None and self.stats_side_stream:
@@ -420,8 +415,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
                 self._capture()
         self.steps += self.n_envs * self.n_steps
         # opt-in: the statistics copy overlaps the update (side stream behind the rollout)
-        self._queue_episode_stats(self.b_done, self.b_epret,
-                                  after=self._rollout_ev if self.stats_side_stream else None)
+        self._queue_episode_stats(after=self._rollout_ev if self.stats_side_stream else None)
         self._maybe_check_peer()
 
     def graph_steps(self):
@@ -429,7 +423,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
         BaseAgent.FUSED_GROUP_MAX; 1 = none): only with the persistent update, whose launch
         stores each step's episode statistics into a host slot of its own."""
         if self.executor_path or getattr(self, 'update_mode', None) != 'persistent' or \
-                not getattr(self, '_stats_fused', False) or self.stats_side_stream:
+                not self._stats_fused or self.stats_side_stream:
             return 1
         # default 8 steps per replay (16 envs 0.1453 -> 0.1435 ms per step,
         # profiles/r06t_graph_steps_ab.txt; 256 envs 0.2553 -> 0.2515 ms once the host's
@@ -456,18 +450,19 @@ class A2C(ExecutorActorCritic, OnPolicy):
             for i in range(S):
                 self._count_update_replay()
                 self.steps += self.n_envs * self.n_steps
-                self._queue_episode_stats(self.b_done, self.b_epret, group_end=i == S - 1)
+                self._queue_episode_stats(group_end=i == S - 1)
                 self._maybe_check_peer()
             n -= S
 
     def _count_update_replay(self):
         """A graph replay that ran the persistent update: one more launch number (the
-        in-launch statistics slots, PPO._setup_fused_stats)."""
-        if getattr(self, '_stats_fused', False) and self.update_mode == 'persistent':
+        in-launch statistics slots, EpisodeStats.setup_fused)."""
+        if self._stats_fused and self.update_mode == 'persistent':
             self._upd_launches += 1
 
     # every rank reaches the same train-step count, so this collective check lines up
     PEER_CHECK_STEPS = 64
+    _fused_steps = 0
 
     def _maybe_check_peer(self):
         """A timed-out peer exchange leaves a sticky error after which every exchange
@@ -476,7 +471,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
         re-broadcasting rank 0's parameters and optimizer state (check_peer_all_reduce)."""
         if not self.distributed or getattr(self, 'peer', None) is None:
             return
-        self._fused_steps = getattr(self, '_fused_steps', 0) + 1
+        self._fused_steps += 1
         every = int(os.environ.get('XA_PEER_CHECK_STEPS', self.PEER_CHECK_STEPS))
         if self._fused_steps % every == 0:
             self.check_peer_all_reduce()
@@ -572,7 +567,7 @@ class A2C(ExecutorActorCritic, OnPolicy):
         finally:
             a.return_kind = saved
         self.steps += self.n_envs * self.n_steps
-        self._queue_episode_stats(self.b_done, self.b_epret)
+        self._queue_episode_stats()
         tm = lambda x: x.transpose(0, 1)  # noqa: E731
         return [tm(self.b_obs), tm(self.b_rew), tm(self.b_act), tm(self.b_val),
                 tm(self.b_done), tm(self.b_logp), tm(self.b_ent), None]

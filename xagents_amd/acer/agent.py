@@ -348,7 +348,7 @@ class ACER(A2C):
                 self._acer_update(*self._gather(self.sample_slots()))
         rec(2)
         self.steps += self.n_envs * self.n_steps
-        self._queue_episode_stats(self.b_done, self.b_epret)
+        self._queue_episode_stats()
 
     def train_step(self):
         self.fused_train_step()

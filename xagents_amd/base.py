@@ -6,16 +6,13 @@ and math go to libxagents_hip.so through the subclasses.
 Differences forced by the device design (documented in DESIGN.md):
 * `envs` is a device vector env (xagents_amd.envs) rather than a list of gym envs;
   it supports len(), envs[0].observation_space / action_space.
-* Episode statistics of a fused rollout are copied back asynchronously and folded
-  into total_rewards / games / done_envs in the reference's step-major, env-minor
-  order at the next train_step (one train_step of lag), so the host never stalls
-  the device between steps.
+* Episode statistics reach total_rewards / games / done_envs asynchronously, one train_step
+  late, in the reference's step-major, env-minor order (xagents_amd/episode_stats.py).
 """
 import os
 import random
 from abc import ABC
 from collections import deque
-from contextlib import nullcontext as _nullcontext
 from datetime import timedelta
 from pathlib import Path
 from time import perf_counter
@@ -91,7 +88,8 @@ class BaseAgent(ABC):
         self.episode_rewards = np.zeros(self.n_envs)
         self.done_envs = 0
         self.supported_action_spaces = Box, Discrete
-        self._pending_stats = None
+        self.episode_stats = None  # on-policy rollouts: EpisodeStats, built with the buffers
+        self.device_status = None  # a persistent update's status word (PPO)
         if seed:
             self.set_seeds(seed)
         self.reset_envs()
@@ -395,227 +393,33 @@ class BaseAgent(ABC):
                 concatenated.append(arg.swapaxes(0, 1).reshape(-1, *arg.shape[2:]))
         return concatenated
 
-    # ---- device episode bookkeeping ----------------------------------------
-    def _queue_episode_stats(self, done_out, epret_out, after=None, group_end=True):
-        """Async D2H copy of one rollout's done flags [N,T+1] and running returns [N,T]
-        (with the persistent update's status word). `after`: an event recorded on the
-        launch stream right after the rollout -- the copy then runs on a side stream
-        behind it, overlapping the update, and the next rollout waits for it
-        (_sync_stats_copy). When the persistent update stores the statistics into its host
-        slots itself (PPO._setup_fused_stats) there is nothing to launch: the step's slot is
-        its launch number modulo XA_PPO_STATS_SLOTS, and the fold checks the number the
-        launch wrote. Steps are folded in groups behind one completion event (`group_end`:
-        the caller closes a group, e.g. after a hipGraph replay of several train steps;
-        XA_STATS_EVERY groups single steps), at most half the slots per group, so that a
-        slot is folded before a later launch reuses it."""
-        if getattr(self, '_stats_fused', False) and after is None and \
-                getattr(self, 'update_mode', None) == 'persistent' and \
-                done_out.data_ptr() == self.b_done.data_ptr():
-            if getattr(self, '_stats_queue', None) is None or \
-                    getattr(self, '_stats_queue_kind', None) != 'fused':
-                self._drain_episode_stats()
-                self._stats_queue = []
-                self._stats_queue_kind = 'fused'
-                self._fused_events = [torch.cuda.Event() for _ in range(4)]
-                self._fused_ev_i = 0
-                self._fused_pending = []
-            self._fused_pending.append(self._upd_launches - 1)
-            self._pending_stats = (done_out, epret_out)
-            every = min(int(os.environ.get('XA_STATS_EVERY', '1')), self.FUSED_GROUP_MAX)
-            if group_end and len(self._fused_pending) >= every or \
-                    len(self._fused_pending) >= self.FUSED_GROUP_MAX:
-                self._close_fused_group()
-            return
-        if self._pending_stats is None or self._pending_stats[0].shape != done_out.shape or \
-                getattr(self, '_stats_queue_kind', None) == 'fused':
-            self._drain_episode_stats()
-            self._host_done = [torch.empty(done_out.shape, dtype=done_out.dtype).pin_memory()
-                               for _ in range(2)]
-            self._host_epret = [torch.empty(epret_out.shape, dtype=epret_out.dtype).pin_memory()
-                                for _ in range(2)]
-            self._host_pack = None
-            self._host_copy_args = {}  # xa_copy_to_host args keyed on the old buffers
-            # one completion event per host slot, reused (a slot is re-recorded only after
-            # its previous copy was folded): no event creation on the step path
-            self._stats_events = [torch.cuda.Event(), torch.cuda.Event()]
-            self._stats_slot = 0
-            self._stats_queue = []
-            self._stats_queue_kind = 'copy'
-        slot = self._stats_slot
-        side = None
-        if after is not None:
-            if getattr(self, '_stats_stream', None) is None:
-                self._stats_stream = torch.cuda.Stream(device=done_out.device)
-                self._stats_warm = False
-            side = self._stats_stream
-            side.wait_event(after)
-        with torch.cuda.stream(side) if side is not None else _nullcontext():
-            pack = getattr(self, '_stats_pack', None)
-            # the statistics leave in ONE xa_copy_to_host launch (stores into the mapped
-            # pinned buffers) instead of D2H DMA copies: 16 envs 0.2859 -> 0.2814 ms per
-            # step (three segments), C2 0.419 -> 0.401 ms (the whole pack as one segment)
-            if pack is not None and pack.numel() >= 65536 and \
-                    done_out.data_ptr() == self.b_done.data_ptr():
-                # done, episode returns and the status word in one copy (a2c/agent.py)
-                if self._host_pack is None:
-                    nd, sd, oe, se, os_ = self._stats_views
-                    self._host_pack = [torch.zeros(pack.shape, dtype=pack.dtype).pin_memory()
-                                       for _ in range(2)]
-                    self._host_done = [h[:nd].view(sd) for h in self._host_pack]
-                    self._host_epret = [h[oe:oe + se[0] * se[1]].view(se)
-                                        for h in self._host_pack]
-                    self._host_status = [h[os_:os_ + 1].view(torch.int32)
-                                         for h in self._host_pack]
-                if side is not None and not self._stats_warm:
-                    # the first device-to-pinned-host copies of a side stream block the
-                    # host for ~7 ms each (MI355X / ROCm 7.2, tools/diag_d2h_side.py): pay
-                    # them here, once, not inside a later step
-                    for _ in range(4):
-                        for h in self._host_pack:
-                            h.copy_(pack, non_blocking=True)
-                    side.synchronize()
-                    self._stats_warm = True
-                if side is None:
-                    self._copy_to_host([(pack, self._host_pack[slot])])
-                else:
-                    self._host_pack[slot].copy_(pack, non_blocking=True)
-            else:
-                segs = [(done_out, self._host_done[slot]), (epret_out, self._host_epret[slot])]
-                status = getattr(self, 'device_status', None)
-                if status is not None:
-                    if getattr(self, '_host_status', None) is None:
-                        self._host_status = [torch.zeros(status.shape, dtype=status.dtype)
-                                             .pin_memory() for _ in range(2)]
-                    segs.append((status, self._host_status[slot]))
-                self._copy_to_host(segs)
-            ev = self._stats_events[slot]
-            ev.record()
-        self._stats_guard = ev if side is not None else None
-        self._stats_queue.append((slot, ev))
-        self._stats_slot ^= 1
-        self._pending_stats = (done_out, epret_out)
-        # keep at most one rollout in flight: fold the previous one now
-        while len(self._stats_queue) > 1:
-            self._fold_item(self._stats_queue.pop(0))
-
+    # ---- device episode bookkeeping (xagents_amd/episode_stats.py) ------------
     # steps folded behind one event: half the in-launch statistics slots (_lib.XA_PPO_STATS_SLOTS)
     FUSED_GROUP_MAX = 8
 
-    def _close_fused_group(self):
-        """One completion event behind the pending fused steps; fold the previous group
-        (its slots are complete once its event is), so one group stays in flight."""
-        if not getattr(self, '_fused_pending', None):
+    def _record_finished(self, finished):
+        """Finished episodes' returns, in step_envs order (one extend: ~1,300 per C2 step)."""
+        if not len(finished):
             return
-        ev = self._fused_events[self._fused_ev_i % len(self._fused_events)]
-        self._fused_ev_i += 1
-        ev.record()
-        self._stats_queue.append(('fused', ev, tuple(self._fused_pending)))
-        self._fused_pending = []
-        while len(self._stats_queue) > 1:
-            self._fold_item(self._stats_queue.pop(0))
-
-    def _fold_item(self, item):
-        if item[0] == 'fused':
-            _, ev, gens = item
-            ev.synchronize()
-            for gen in gens:
-                self._fold_stats(None, None, gen)
-        else:
-            self._fold_stats(*item)
-
-    def _copy_to_host(self, segs):
-        """(device, pinned host) tensor pairs to the host in ONE xa_copy_to_host launch on
-        the current stream (at 16 envs three D2H DMA copies cost ~14 us of stream time per
-        train step; the launch stores the same words into the mapped host buffers)."""
-        if not segs[0][0].is_cuda:
-            for d, h in segs:
-                h.copy_(d, non_blocking=True)
-            return
-        from xagents_amd._lib import XaHostCopyArgs, call, mapped_address, stream
-        import ctypes
-        key = tuple((d.data_ptr(), h.data_ptr(), d.numel() * d.element_size()) for d, h in segs)
-        cache = self.__dict__.setdefault('_host_copy_args', {})
-        a = cache.get(key)
-        if a is None:
-            a = XaHostCopyArgs()
-            a.n_segments = len(segs)
-            for i, (d, h) in enumerate(segs):
-                assert d.is_contiguous() and h.is_contiguous() and h.is_pinned()
-                a.src[i], a.dst[i] = d.data_ptr(), mapped_address(h)
-                a.bytes[i] = d.numel() * d.element_size()
-            cache[key] = a
-        call('xa_copy_to_host', ctypes.byref(a), stream())
-
-    def _sync_stats_copy(self):
-        """The launch stream waits for a side-stream statistics copy still reading the
-        rollout buffers (call before every rollout launch)."""
-        ev = getattr(self, '_stats_guard', None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-            self._stats_guard = None
-
-    def _fold_stats(self, slot, ev, gen=None):
-        if ev is not None:
-            ev.synchronize()
-        if gen is not None:
-            from xagents_amd._lib import XA_PPO_STATS_SLOTS
-            slot = gen % XA_PPO_STATS_SLOTS
-        if gen is None:
-            host_done, host_epret, host_status = (self._host_done[slot], self._host_epret[slot],
-                                                  getattr(self, '_host_status', None))
-            host_status = host_status[slot] if host_status is not None else None
-        else:
-            # the update launch number `gen` stored this slot (checked: a launch the host
-            # did not count would otherwise fold another step's statistics)
-            host_done, host_epret, host_status = (self._fused_done[slot],
-                                                  self._fused_epret[slot],
-                                                  self._fused_host_status[slot])
-            got = int(self._fused_gen[slot].item())
-            # a launch that aborted (exchange timeout) may never have stored its slot: the
-            # device status word names that cause, so it is checked before the slot's number
-            if got != gen:
-                status = getattr(self, 'device_status', None)
-                if status is not None and int(status.max().item()):
-                    raise RuntimeError(
-                        f'{self.__class__.__name__}: an in-launch exchange of the persistent '
-                        f'update timed out (device status word set); the parameters are '
-                        f'invalid')
-                raise RuntimeError(f'{self.__class__.__name__}: episode statistics slot {slot} '
-                                   f'holds update launch {got}, expected {gen}')
-        if getattr(self, 'device_status', None) is not None and host_status is not None and \
-                int(host_status.max()):
-            raise RuntimeError(
-                f'{self.__class__.__name__}: an in-launch exchange of the persistent update '
-                f'timed out (device status word set); the parameters are invalid')
-        done = host_done.numpy()[:, 1:]
-        epret = host_epret.numpy()
-        t_idx, env_idx = np.nonzero(done.T)  # step-major, env-minor like step_envs
-        finished = epret[env_idx, t_idx]
         if self.history_checkpoint:
             for ret in finished:
                 self.update_history(ret)
-        # (one extend, not a Python append per finished episode: at 256 envs ~1,300 episodes
-        # end per train step, and the fold is host time on every step)
         self.total_rewards.extend(finished.astype(np.float64).tolist())
         self.games += len(finished)
         self.done_envs += len(finished)
-        self.episode_rewards = epret[:, -1] * (1.0 - done[:, -1])
-        self.dones = (done[:, -1] != 0).tolist()
+
+    _stats_fused = property(lambda self: self.episode_stats is not None and
+                            self.episode_stats.fused_on)
+
+    def _queue_episode_stats(self, after=None, group_end=True):
+        self.episode_stats.queue(after, group_end)
+
+    def _sync_stats_copy(self):
+        self.episode_stats.sync_copy()
 
     def _drain_episode_stats(self):
-        if getattr(self, '_fused_pending', None):
-            self._close_fused_group()
-        while getattr(self, '_stats_queue', None):
-            self._fold_item(self._stats_queue.pop(0))
-        # a side-stream copy reads the status word before the step's update ends: the
-        # last update's status is read here
-        status = getattr(self, 'device_status', None)
-        if status is not None and (getattr(self, '_stats_stream', None) is not None or
-                                   getattr(self, '_stats_fused', False)) and \
-                int(status.max().item()):
-            raise RuntimeError(
-                f'{self.__class__.__name__}: an in-launch exchange of the persistent update '
-                f'timed out (device status word set); the parameters are invalid')
+        if self.episode_stats is not None:
+            self.episode_stats.drain()
 
     def fit(
         self,
@@ -704,6 +508,7 @@ class OffPolicy(BaseAgent, ABC):
         self.per_beta = self.per_beta_start = per_beta
         self.per_beta_steps = per_beta_steps
         self.per = None  # the PrioritizedSampler, built with the rings (_setup_offpolicy)
+        self.step_stats = None  # the env steps' StepStats (_setup_offpolicy)
 
     # ---- prioritized replay (xagents_amd/per.py) ------------------------------------
     # agents whose learner phase samples through the PrioritizedSampler (DQN, SAC)
@@ -774,6 +579,7 @@ class OffPolicy(BaseAgent, ABC):
         the per-step episode-stat rows copied back asynchronously."""
         import torch.distributed as dist
         from xagents_amd._lib import XaReplayStepArgs
+        from xagents_amd.episode_stats import StepStats
         from xagents_amd.replay import DeviceReplay
         # data parallel over env shards: each rank samples its own buffers, gradients
         # are all-reduced (sum) and scaled by 1 / world before Adam
@@ -795,13 +601,7 @@ class OffPolicy(BaseAgent, ABC):
                                           self.per_eps, self.seed or 0)
         self._step_args = XaReplayStepArgs()
         env.fill_step_args(self._step_args)
-        n, K = self.n_envs, self._STATS_ROWS
-        # per step: [done row | episode-return row] (one copy per step fills both)
-        self._st = torch.zeros(K, 2, n, dtype=torch.float32, device=self.device)
-        self._st_done = self._st[:, 0]
-        self._st_epret = self._st[:, 1]
-        self._st_row = 0
-        self._st_host = []
+        self.step_stats = StepStats(self, self._STATS_ROWS)
 
     def _env_step(self, actions, store=True):
         """One xa_replay_env_step: every env steps with `actions` (device) and, when
@@ -812,17 +612,13 @@ class OffPolicy(BaseAgent, ABC):
         else:
             a.ring_states = None
             a.actions, a.act_bytes = actions.data_ptr(), self.replay.act_bytes
-        r = self._st_row
-        a.out_dones = self._st_done[r].data_ptr()
-        a.done_epret = self._st_epret[r].data_ptr()
+        a.out_dones, a.done_epret = self.step_stats.ptrs[self.step_stats.row]
         if store and self.per is not None:
             self.per.mark()  # reads the ring counters before the step's append
         self.envs.step_into(a, actions)
         if store:
             self.replay.appended()
-        self._st_row += 1
-        if self._st_row == self._STATS_ROWS:
-            self._flush_offpolicy_stats()
+        self.step_stats.advance()
 
     def _play_actions(self):
         """Device actions of the play policy for every env (subclasses)."""
@@ -854,37 +650,10 @@ class OffPolicy(BaseAgent, ABC):
         """Raise on an error a persistent launch reported through its device status word
         (subclasses; called with every statistics flush, so no extra sync per step)."""
 
-    def _flush_offpolicy_stats(self):
-        self._device_checks()
-        rows = self._st_row
-        if rows == 0:
-            return
-        h = torch.empty(rows, 2, self.n_envs).pin_memory()
-        h.copy_(self._st[:rows], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._st_host.append((h[:, 0], h[:, 1], ev))
-        self._st_row = 0
-        while len(self._st_host) > 1:
-            self._fold_offpolicy_stats(*self._st_host.pop(0))
-
-    def _fold_offpolicy_stats(self, hd, he, ev):
-        ev.synchronize()
-        d, e = hd.numpy(), he.numpy()
-        for t in range(d.shape[0]):  # step-major, env-minor like step_envs
-            for i in np.nonzero(d[t])[0]:
-                if self.history_checkpoint:
-                    self.update_history(float(e[t, i]))
-                self.total_rewards.append(float(e[t, i]))
-                self.games += 1
-                self.done_envs += 1
-
     def _drain_episode_stats(self):
         super()._drain_episode_stats()
-        if hasattr(self, '_st_host'):
-            self._flush_offpolicy_stats()
-            while self._st_host:
-                self._fold_offpolicy_stats(*self._st_host.pop(0))
+        if self.step_stats is not None:
+            self.step_stats.drain()
 
     def _sync_params(self, *models):
         if self.distributed:

@@ -495,26 +495,20 @@ class DDPG(OffPolicy):
         if self._stage_host:
             self._stage, dp = mapped_pinned((2, self.n_envs), torch.float32)
             self._stage_ptrs = (dp, dp + 4 * self.n_envs)
+            self._stage_np = self._stage.numpy()
             self._stage_ev = torch.cuda.Event()
             self._stage_rows = 0
         else:
             self._stage = torch.zeros(2, self.n_envs, dtype=torch.float32, device=self.device)
             self._stage_ptrs = (self._stage[0].data_ptr(), self._stage[1].data_ptr())
-        self._stage_done, self._stage_epret = self._stage[0], self._stage[1]
         # the env step's two launches launched directly, or (XA_TD3_STEP_GRAPH=1) replayed
         # from a hipGraph
         # (direct by default: C5 0.1069 -> 0.1047 ms per step, profiles/r06r_td3_step_graph_ab.txt)
         self._step_graph = os.environ.get('XA_TD3_STEP_GRAPH', '0') == '1'
 
-    def _fold_step_row(self, d, e):
-        """One step's episode statistics (host rows), env order as step_envs; the device
-        status word is checked every _STATS_ROWS steps (as the statistics flush does)."""
-        for i in np.nonzero(d)[0]:
-            if self.history_checkpoint:
-                self.update_history(float(e[i]))
-            self.total_rewards.append(float(e[i]))
-            self.games += 1
-            self.done_envs += 1
+    def _fold_stage(self):
+        """The mapped host stage's [1, n] rows; device checks as often as the block flush."""
+        self.step_stats.fold(self._stage_np[None])
         self._stage_rows += 1
         if self._stage_rows == self._STATS_ROWS:
             self._stage_rows = 0
@@ -539,7 +533,7 @@ class DDPG(OffPolicy):
         envs with a host-side pre_step (raw-frame Atari) stay on the eager path."""
         if self.envs.has_pre_step:
             actions = self.get_step_actions()
-            row = self._st_row
+            row = self.step_stats.row
             self._env_step(actions)
             self.steps += self.n_envs
             dones = self._host_row_dones(row)
@@ -554,15 +548,13 @@ class DDPG(OffPolicy):
                 # the step's rows land in mapped host memory: one event wait, no copies
                 self._stage_ev.record()
                 self._stage_ev.synchronize()
-                dones = self._stage[0].numpy().copy()
-                self._fold_step_row(dones, self._stage[1].numpy())
+                dones = self._stage_np[0].copy()
+                self._fold_stage()
             else:
-                r = self._st_row
-                self._st[r].copy_(self._stage)  # both rows in one copy
-                self._st_row += 1
-                if self._st_row == self._STATS_ROWS:
-                    self._flush_offpolicy_stats()
-                dones = self._stage_done.cpu().numpy()
+                ss = self.step_stats
+                ss.block[ss.row].copy_(self._stage)  # both rows in one copy
+                ss.advance()
+                dones = self._stage[0].cpu().numpy()
             self.replay.appended()
             self.steps += self.n_envs
         if self.distributed:
@@ -582,4 +574,4 @@ class DDPG(OffPolicy):
     def _host_row_dones(self, row):
         """The done flags of the step just taken (the reference returns them from the
         numpy step_envs; here one small synchronous copy of the step's stats row)."""
-        return self._st_done[row].cpu().numpy()
+        return self.step_stats.block[row, 0].cpu().numpy()

@@ -28,6 +28,7 @@ import torch
 from xagents_amd import kernels
 from xagents_amd._lib import (XA_DIST_DIAG_GAUSSIAN, XA_LOSS_PPO, XA_RETURNS_GAE,
                               XaHeadGradArgs, XaReplayStepArgs, call, stream)
+from xagents_amd.episode_stats import EpisodeStats
 from xagents_amd.layers import LayerExecutor
 
 
@@ -63,6 +64,7 @@ class ExecutorRollout:
         self.b_logp, self.b_ent = torch.zeros(N, T, **f32), torch.zeros(N, T, **f32)
         self.b_done = torch.zeros(N, T + 1, **f32)
         self.b_epret = torch.zeros(N, T, **f32)
+        self.episode_stats = EpisodeStats(self, self.b_done, self.b_epret)
         if returns:
             if self.gaussian:
                 self.b_act = torch.zeros(N, T, A, **f32)
@@ -347,5 +349,5 @@ class ExecutorActorCritic(ExecutorRollout):
         self._executor_rollout()
         self._executor_update()
         self.steps += self.n_envs * self.n_steps
-        self._queue_episode_stats(self.b_done, self.b_epret)
+        self._queue_episode_stats()
 

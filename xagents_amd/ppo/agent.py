@@ -64,11 +64,11 @@ class PPO(A2C):
     def _setup_update(self):
         # a re-plan (a peer timeout dropping to the chain, a new permutation source) starts
         # with no statistics stored by an update launch: fold what earlier launches stored,
-        # and only `_setup_fused_stats` (persistent mode) turns the fused slots back on
+        # and only `setup_fused` (persistent mode) turns the fused transport back on
         # (a chain step must not fold the last persistent launch's slot again)
-        if getattr(self, '_stats_fused', False):
+        if self._stats_fused:
             self._drain_episode_stats()
-        self._stats_fused = False
+        self.episode_stats.fused_on = False
         # optimizer step placement of the chain: 'prologue' (next minibatch's xa_ac_grad
         # recomputes it in every block) or 'kernel' (a standalone xa_clip_adam launch)
         self._opt_kernel = os.environ.get('XA_PPO_OPT', 'prologue') == 'kernel'
@@ -225,7 +225,7 @@ class PPO(A2C):
         # statistics copy (XA_STATS_SIDE_STREAM=1) can overlap the update, so it forces the
         # spread grid.
         place = os.environ.get('XA_PPO_PLACE', 'auto')
-        if getattr(self, 'stats_side_stream', False) and place != 'local':
+        if self.stats_side_stream and place != 'local':
             place = 'spread'
         if place == 'spread':
             u.placement = _lib.XA_PPO_PLACE_SPREAD
@@ -243,38 +243,10 @@ class PPO(A2C):
             u.dp_world, u.dp_rank = self.world_size, self.rank
             for r, ptr in enumerate(self.dp_blocks.pointers):
                 u.dp_blocks[r] = ptr
-        self._setup_fused_stats(u)
+        self.episode_stats.setup_fused(u)  # the statistics leave inside the update launch
         self._uargs = u
         self.update_mode = 'persistent'
         self.update_blocks = n_blocks
-
-    def _setup_fused_stats(self, u):
-        """The train step's episode statistics (done flags, running returns, the status word:
-        the packed buffer a2c/agent.py lays out) leave the device inside the update launch,
-        into XA_PPO_STATS_SLOTS mapped pinned host slots chosen by the launch number -- no
-        xa_copy_to_host launch per train step, and several train steps per graph replay. Off with XA_STATS_IN_UPDATE=0 or the opt-in
-        side-stream copy."""
-        u.stats_words = 0
-        self._stats_fused = False
-        if os.environ.get('XA_STATS_IN_UPDATE', '1') == '0' or \
-                getattr(self, 'stats_side_stream', False):
-            return
-        nd, sd, oe, se, os_ = self._stats_views
-        nw = os_ + 1  # through the status word
-        if getattr(self, '_fused_host', None) is None or self._fused_host[0].numel() != nw + 1:
-            self._fused_host, self._fused_dev = zip(*(
-                _lib.mapped_pinned(nw + 1, torch.float32)
-                for _ in range(_lib.XA_PPO_STATS_SLOTS)))
-            self._fused_done = [h[:nd].view(sd) for h in self._fused_host]
-            self._fused_epret = [h[oe:oe + se[0] * se[1]].view(se) for h in self._fused_host]
-            self._fused_host_status = [h[os_:os_ + 1].view(torch.int32)
-                                       for h in self._fused_host]
-            self._fused_gen = [h[nw:nw + 1].view(torch.int32) for h in self._fused_host]
-        u.stats_src = self._stats_pack.data_ptr()
-        for i, dp in enumerate(self._fused_dev):
-            u.stats_dst[i] = dp
-        u.stats_words = nw
-        self._stats_fused = True
 
     def set_minibatch_permutation(self, perm):
         """Parity mode: the fused update takes every epoch's shuffle from `perm`, an
@@ -342,7 +314,7 @@ class PPO(A2C):
         kernels.rollout(a)
         kernels.counter_bump(self.rng_counter)
         self.steps += self.n_envs * self.n_steps
-        self._queue_episode_stats(self.b_done, self.b_epret)
+        self._queue_episode_stats()
         B = self.batch_size
         return [self.b_obs.reshape(B, -1), self.b_act.reshape(B).float(),
                 self.b_ret.reshape(B), self.b_val.reshape(B), self.b_logp.reshape(B)]

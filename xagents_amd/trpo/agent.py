@@ -169,7 +169,7 @@ class TRPO(PPO):
         from Python; after one eager pass they are captured once and replayed."""
         self._rollout_phase.run(self._rollout_kernels, self.use_graph)
         self.steps += self.n_envs * self.n_steps
-        self._queue_episode_stats(self.b_done, self.b_epret)
+        self._queue_episode_stats()
 
     def _play_chunk(self):
         """play(): one eager rollout (actor samples); env 0's rewards and step dones."""
