@@ -630,6 +630,15 @@ int xa_dqn_td_grad_w(const float* q, const float* q_next_target, const float* q_
                      int n_actions, float gamma, float huber_delta, float* dq, float* loss,
                      int* adam_step, const float* is_weights, float* td_abs, void* stream);
 
+/* xa_dqn_td_grad_w (the same kernel) for n-step replay: discounts [batch] (in, optional) is
+ * each sample's own bootstrap discount gamma^m (xa_ring_gather_nstep writes it), taken in
+ * place of gamma in y = v' discount_b + r. NULL: gamma, the bytes of xa_dqn_td_grad_w. */
+int xa_dqn_td_grad_n(const float* q, const float* q_next_target, const float* q_next_online,
+                     const int* actions, const float* rewards, const float* dones, int batch,
+                     int n_actions, float gamma, float huber_delta, float* dq, float* loss,
+                     int* adam_step, const float* is_weights, float* td_abs,
+                     const float* discounts, void* stream);
+
 /* Quantile-regression DQN (Dabney et al., https://arxiv.org/abs/1710.10044; csrc/qr.hip,
  * csrc/qr_terms.hpp states the arithmetic). A network output row theta is [n_actions]
  * [n_quantiles], action-major: output a N + i is quantile i of action a, at the midpoint
@@ -660,6 +669,14 @@ int xa_qr_td_grad(const float* theta, const float* theta_next_target,
                   const float* dones, int batch, int n_actions, int n_quantiles, float gamma,
                   float huber_kappa, float* dtheta, float* loss, int* adam_step,
                   const float* is_weights, float* td_abs, void* stream);
+/* xa_qr_td_grad (the same kernel) for n-step replay: discounts [batch] (in, optional) is each
+ * sample's own gamma^m in place of gamma in y_j; NULL: gamma, the bytes of xa_qr_td_grad. */
+int xa_qr_td_grad_n(const float* theta, const float* theta_next_target,
+                    const float* theta_next_online, const int* actions, const float* rewards,
+                    const float* dones, int batch, int n_actions, int n_quantiles, float gamma,
+                    float huber_kappa, float* dtheta, float* loss, int* adam_step,
+                    const float* is_weights, float* td_abs, const float* discounts,
+                    void* stream);
 
 /* The Q head (the last dense layer, N <= 8 actions: xa_gemm's row-dot shape) with DQN's
  * per-row step fused into the same launch. mode 0: actions[m] = first argmax of row m
@@ -772,6 +789,40 @@ typedef struct XaReplayStepArgs {
 } XaReplayStepArgs;
 
 int xa_replay_env_step(const XaReplayStepArgs* args, void* stream);
+
+/* n-step gather (csrc/nstep_terms.hpp states the arithmetic): xa_ring_gather_fields' launch for
+ * multi-step targets, on the XA_RING_DEQUE rings xa_replay_env_step appends to. For item b
+ * with slots[b] = env capacity + i and c = ring_count[env]: newest = (c - 1) mod capacity,
+ * avail = ((newest - i) mod capacity) + 1, m_max = min(n_steps, avail), L = the first k in
+ * 0 .. m_max - 1 with ring_dones[(i + k) mod capacity] != 0 (none: m_max - 1), m = L + 1. The
+ * walk neither crosses an episode end nor passes the ring's newest entry. Written:
+ *   states[b] = ring_states[i], actions[b] = ring_actions[i] (bytes),
+ *   new_states[b] = ring_new_states[(i + L) mod capacity], dones[b] = ring_dones[(i + L) ...],
+ *   rewards[b] = R: R = r_L, then R = r_k + gamma R for k = L - 1 .. 0 (f32, this order),
+ *   discounts[b] = gamma^m: g = gamma, then g = g gamma another m - 1 times.
+ * n_steps = 1: the bytes of xa_ring_gather_fields and discounts[b] = gamma. slots may live in
+ * mapped pinned host memory; the counters are read on the device, so a captured launch follows
+ * the ring. 1 <= n_steps <= min(64, capacity) and ring_kind == XA_RING_DEQUE, anything else is
+ * an error before a launch. */
+typedef struct XaNstepGatherArgs {
+  const void* ring_states;
+  const void* ring_new_states;
+  const void* ring_actions;
+  const float* ring_rewards;
+  const float* ring_dones;
+  const int64_t* ring_count;
+  int64_t obs_bytes, act_bytes, capacity;
+  int ring_kind, n_steps, n_items;
+  float gamma;
+  const int64_t* slots;
+  void* states;
+  void* actions;
+  float* rewards;
+  float* dones;
+  void* new_states;
+  float* discounts;
+} XaNstepGatherArgs;
+int xa_ring_gather_nstep(const XaNstepGatherArgs* args, void* stream);
 
 /* AtariWrapper.step / reset on device (xagents/utils/common.py:67-142, the per-env
  * `env.step` + `env.reset` of BaseAgent.step_envs, base.py:388-426, for Atari envs).

@@ -7,9 +7,10 @@
 //     xagents/utils/buffers.py:59-98) and ReplayBuffer2 (row-0 overwrite when full,
 //     buffers.py:101-148) append / gather. The ring position arithmetic that
 //     reproduces the reference's index semantics lives on the host; the kernels move
-//     the bytes.
+//     the bytes. The n-step gather (nstep_terms.hpp) reads the append counters on the device.
 #include "../../include/xagents_hip.h"
 #include "env_step.hpp"
+#include "nstep_terms.hpp"
 #include "td_terms.hpp"
 #include "xa_common.hpp"
 
@@ -60,14 +61,16 @@ __global__ void dqn_act_kernel(const float* __restrict__ q, int n, int A,
 // DQN.get_targets + the loss gradient (dqn/agent.py:118-171), td_terms.hpp's dqn_target and
 // dqn_td on v' = double ? Qt(s')[argmax Q(s')] : max_a Qt(s') (minimize on a [B] loss sums);
 // dQ is zero off the action (y copies Q there). is_weights / td_abs (prioritized replay, both
-// optional): td_terms.hpp's weighted / td_abs_of
+// optional): td_terms.hpp's weighted / td_abs_of; discounts (n-step replay, optional): its
+// discount_of
 __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restrict__ q_next_t,
                               const float* __restrict__ q_next_o, const int* __restrict__ act,
                               const float* __restrict__ rew, const float* __restrict__ done,
                               int B, int A, float gamma, float huber, float* __restrict__ dq,
                               float* __restrict__ loss, int* __restrict__ adam_step,
                               const float* __restrict__ is_weights,
-                              float* __restrict__ td_abs) {
+                              float* __restrict__ td_abs,
+                              const float* __restrict__ discounts) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (adam_step && b == 0) adam_step[0] += 1;  // the update's t += 1, one launch fewer
   if (b >= B) return;
@@ -79,7 +82,7 @@ __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restri
     v = qt[0];
     for (int a = 1; a < A; ++a) v = fmaxf(v, qt[a]);
   }
-  const float y = xa_td::dqn_target(v, done[b], gamma, rew[b]);
+  const float y = xa_td::dqn_target(v, done[b], xa_td::discount_of(gamma, discounts, b), rew[b]);
   const int ab = act[b];
   const float diff = y - q[(size_t)b * A + ab];
   float dqa, l;
@@ -90,6 +93,19 @@ __global__ void dqn_td_kernel(const float* __restrict__ q, const float* __restri
   if (td_abs) td_abs[b] = xa_td::td_abs_of(diff);
 }
 
+// this workgroup's share of one item's nb bytes, s -> d, the item spread over blockIdx.x:
+// 16-B moves where the size and both addresses allow, bytes otherwise
+XA_DEV void ring_copy_item(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int64_t nb) {
+  if ((nb & 15) == 0 && ((uintptr_t)s & 15) == 0 && ((uintptr_t)d & 15) == 0) {
+    const int64_t n16 = nb >> 4;
+    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n16; e += (int64_t)gridDim.x * 256)
+      reinterpret_cast<uint4*>(d)[e] = reinterpret_cast<const uint4*>(s)[e];
+  } else {
+    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < nb; e += (int64_t)gridDim.x * 256)
+      d[e] = s[e];
+  }
+}
+
 // ring[slot[i]] <- src[i] for n_items items of item_bytes each (append)
 __global__ __launch_bounds__(256) void ring_scatter_kernel(const uint8_t* __restrict__ src,
                                                            uint8_t* __restrict__ ring,
@@ -97,16 +113,7 @@ __global__ __launch_bounds__(256) void ring_scatter_kernel(const uint8_t* __rest
                                                            int n_items, int64_t item_bytes) {
   const int i = blockIdx.y;
   if (i >= n_items) return;
-  const uint8_t* s = src + (int64_t)i * item_bytes;
-  uint8_t* d = ring + slots[i] * item_bytes;
-  if ((item_bytes & 15) == 0 && ((uintptr_t)s & 15) == 0 && ((uintptr_t)d & 15) == 0) {
-    const int64_t n16 = item_bytes >> 4;
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n16; e += (int64_t)gridDim.x * 256)
-      reinterpret_cast<uint4*>(d)[e] = reinterpret_cast<const uint4*>(s)[e];
-  } else {
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < item_bytes; e += (int64_t)gridDim.x * 256)
-      d[e] = s[e];
-  }
+  ring_copy_item(src + (int64_t)i * item_bytes, ring + slots[i] * item_bytes, item_bytes);
 }
 
 // dst[i] <- ring[slot[i]] (sample gather, env-major batch order)
@@ -116,16 +123,7 @@ __global__ __launch_bounds__(256) void ring_gather_kernel(const uint8_t* __restr
                                                           int n_items, int64_t item_bytes) {
   const int i = blockIdx.y;
   if (i >= n_items) return;
-  const uint8_t* s = ring + slots[i] * item_bytes;
-  uint8_t* d = dst + (int64_t)i * item_bytes;
-  if ((item_bytes & 15) == 0 && ((uintptr_t)s & 15) == 0 && ((uintptr_t)d & 15) == 0) {
-    const int64_t n16 = item_bytes >> 4;
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n16; e += (int64_t)gridDim.x * 256)
-      reinterpret_cast<uint4*>(d)[e] = reinterpret_cast<const uint4*>(s)[e];
-  } else {
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < item_bytes; e += (int64_t)gridDim.x * 256)
-      d[e] = s[e];
-  }
+  ring_copy_item(ring + slots[i] * item_bytes, dst + (int64_t)i * item_bytes, item_bytes);
 }
 
 // every field of a sampled batch in one launch: blockIdx.z = field (wave-uniform), the
@@ -134,15 +132,51 @@ __global__ __launch_bounds__(256) void ring_gather_fields_kernel(XaGatherArgs a)
   const int i = blockIdx.y, f = blockIdx.z;
   if (i >= a.n_items || f >= a.n_fields) return;
   const int64_t nb = a.field[f].item_bytes;
-  const uint8_t* s = static_cast<const uint8_t*>(a.field[f].ring) + a.slots[i] * nb;
-  uint8_t* d = static_cast<uint8_t*>(a.field[f].dst) + (int64_t)i * nb;
-  if ((nb & 15) == 0 && ((uintptr_t)s & 15) == 0 && ((uintptr_t)d & 15) == 0) {
-    const int64_t n16 = nb >> 4;
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n16; e += (int64_t)gridDim.x * 256)
-      reinterpret_cast<uint4*>(d)[e] = reinterpret_cast<const uint4*>(s)[e];
-  } else {
-    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < nb; e += (int64_t)gridDim.x * 256)
-      d[e] = s[e];
+  ring_copy_item(static_cast<const uint8_t*>(a.field[f].ring) + a.slots[i] * nb,
+                 static_cast<uint8_t*>(a.field[f].dst) + (int64_t)i * nb, nb);
+}
+
+// the n-step transition of every sampled slot in one launch (nstep_terms.hpp states it): the
+// grid is the plain gather's, (observation chunks, items). Every wave redoes its item's walk:
+// lane k < m_max loads step k's done (and reward), a ballot and find-first give L, and the
+// Horner chain runs over readlanes -- at most 64 scalars per wave, L2 hits. The workgroup then
+// copies its share of the two observation rows; workgroup x == 0 writes the item's action,
+// reward, done and discount. No LDS, no atomics.
+__global__ __launch_bounds__(256) void ring_gather_nstep_kernel(XaNstepGatherArgs a) {
+  const int item = blockIdx.y;
+  if (item >= a.n_items) return;
+  const int lane = threadIdx.x & (xa_nstep::kMaxSteps - 1);
+  const int64_t cap = a.capacity;
+  const int64_t slot = a.slots[item];
+  const int64_t env = slot / cap, i = slot - env * cap;
+  const int64_t base = env * cap;
+  const int m_max = xa_nstep::max_steps(a.ring_count[env], cap, i, a.n_steps);  // wave-uniform
+  const bool mine = lane < m_max;
+  const int64_t at = base + xa_nstep::wrap(i + (mine ? lane : 0), cap);
+  const float d_k = a.ring_dones[at];
+  const int L = xa_nstep::last_step(__ballot(mine && d_k != 0.0f), m_max);
+  const int64_t last = base + xa_nstep::wrap(i + L, cap);
+
+  const uint8_t* rs = static_cast<const uint8_t*>(a.ring_states);
+  const uint8_t* rn = static_cast<const uint8_t*>(a.ring_new_states);
+  ring_copy_item(rs + slot * a.obs_bytes, static_cast<uint8_t*>(a.states) + item * a.obs_bytes,
+                 a.obs_bytes);
+  ring_copy_item(rn + last * a.obs_bytes,
+                 static_cast<uint8_t*>(a.new_states) + item * a.obs_bytes, a.obs_bytes);
+  if (blockIdx.x != 0) return;
+  const uint8_t* ra = static_cast<const uint8_t*>(a.ring_actions) + slot * a.act_bytes;
+  uint8_t* da = static_cast<uint8_t*>(a.actions) + item * a.act_bytes;
+  for (int64_t e = threadIdx.x; e < a.act_bytes; e += 256) da[e] = ra[e];
+  if (threadIdx.x >= xa_nstep::kMaxSteps) return;  // wave 0 owns the scalars
+  const int r_k = __float_as_int(a.ring_rewards[at]);
+  float R = __int_as_float(__builtin_amdgcn_readlane(r_k, L));
+  for (int k = L - 1; k >= 0; --k)
+    R = xa_nstep::fold(__int_as_float(__builtin_amdgcn_readlane(r_k, k)), a.gamma, R);
+  const float d_L = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d_k), L));
+  if (lane == 0) {
+    a.rewards[item] = R;
+    a.dones[item] = d_L;
+    a.discounts[item] = xa_nstep::discount(a.gamma, L + 1);
   }
 }
 
@@ -318,20 +352,31 @@ extern "C" int xa_dqn_act(const float* q, int n, int n_actions, const int* rando
   return 0;
 }
 
+extern "C" int xa_dqn_td_grad_n(const float* q, const float* q_next_target,
+                                const float* q_next_online, const int* actions,
+                                const float* rewards, const float* dones, int batch,
+                                int n_actions, float gamma, float huber_delta, float* dq,
+                                float* loss, int* adam_step, const float* is_weights,
+                                float* td_abs, const float* discounts, void* stream) {
+  XA_CHECK_ARG(q && q_next_target && actions && rewards && dones && dq && batch > 0 &&
+                   n_actions > 0,
+               "xa_dqn_td_grad: bad arguments");
+  hipLaunchKernelGGL(dqn_td_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, q,
+                     q_next_target, q_next_online, actions, rewards, dones, batch, n_actions,
+                     gamma, huber_delta, dq, loss, adam_step, is_weights, td_abs, discounts);
+  XA_CHECK_LAUNCH("xa_dqn_td_grad");
+  return 0;
+}
+
 extern "C" int xa_dqn_td_grad_w(const float* q, const float* q_next_target,
                                 const float* q_next_online, const int* actions,
                                 const float* rewards, const float* dones, int batch,
                                 int n_actions, float gamma, float huber_delta, float* dq,
                                 float* loss, int* adam_step, const float* is_weights,
                                 float* td_abs, void* stream) {
-  XA_CHECK_ARG(q && q_next_target && actions && rewards && dones && dq && batch > 0 &&
-                   n_actions > 0,
-               "xa_dqn_td_grad: bad arguments");
-  hipLaunchKernelGGL(dqn_td_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, q,
-                     q_next_target, q_next_online, actions, rewards, dones, batch, n_actions,
-                     gamma, huber_delta, dq, loss, adam_step, is_weights, td_abs);
-  XA_CHECK_LAUNCH("xa_dqn_td_grad");
-  return 0;
+  return xa_dqn_td_grad_n(q, q_next_target, q_next_online, actions, rewards, dones, batch,
+                          n_actions, gamma, huber_delta, dq, loss, adam_step, is_weights, td_abs,
+                          nullptr, stream);
 }
 
 extern "C" int xa_dqn_td_grad(const float* q, const float* q_next_target,
@@ -382,6 +427,28 @@ extern "C" int xa_ring_gather_fields(const XaGatherArgs* p, void* stream) {
   hipLaunchKernelGGL(ring_gather_fields_kernel, dim3(gx, a.n_items, a.n_fields), dim3(256), 0,
                      (hipStream_t)stream, a);
   XA_CHECK_LAUNCH("xa_ring_gather_fields");
+  return 0;
+}
+
+extern "C" int xa_ring_gather_nstep(const XaNstepGatherArgs* p, void* stream) {
+  XA_CHECK_ARG(p != nullptr, "xa_ring_gather_nstep: null args");
+  const XaNstepGatherArgs& a = *p;
+  XA_CHECK_ARG(a.ring_states && a.ring_new_states && a.ring_actions && a.ring_rewards &&
+                   a.ring_dones && a.ring_count && a.slots && a.states && a.new_states &&
+                   a.actions && a.rewards && a.dones && a.discounts,
+               "xa_ring_gather_nstep: null ring, counter, slots or destination");
+  XA_CHECK_ARG(a.n_items > 0 && a.obs_bytes > 0 && a.act_bytes > 0 && a.capacity > 0,
+               "xa_ring_gather_nstep: n_items, obs_bytes, act_bytes and capacity must be > 0");
+  XA_CHECK_ARG(a.ring_kind == XA_RING_DEQUE,
+               "xa_ring_gather_nstep: ring kind %d: only the deque ring keeps an env's "
+               "consecutive transitions in consecutive slots",
+               a.ring_kind);
+  XA_CHECK_ARG(a.n_steps >= 1 && a.n_steps <= xa_nstep::kMaxSteps && a.n_steps <= a.capacity,
+               "xa_ring_gather_nstep: n_steps %d outside 1 .. min(%d, capacity %lld)", a.n_steps,
+               xa_nstep::kMaxSteps, (long long)a.capacity);
+  hipLaunchKernelGGL(ring_gather_nstep_kernel, dim3(ring_grid_x(a.obs_bytes), a.n_items),
+                     dim3(256), 0, (hipStream_t)stream, a);
+  XA_CHECK_LAUNCH("xa_ring_gather_nstep");
   return 0;
 }
 

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void qr_td_kernel(
     const float* __restrict__ rew, const float* __restrict__ done, int B, int A, int N,
     float gamma, float kappa, float* __restrict__ dtheta, float* __restrict__ loss,
     int* __restrict__ adam_step, const float* __restrict__ is_weights,
-    float* __restrict__ td_abs) {
+    float* __restrict__ td_abs, const float* __restrict__ discounts) {
   __shared__ float y_strip[kWaves][kMaxQuantiles];
   const int lane = threadIdx.x & (kLanes - 1), wave = threadIdx.x / kLanes;
   if (adam_step && blockIdx.x == 0 && threadIdx.x == 0)
@@ -64,8 +64,8 @@ __global__ __launch_bounds__(kBlock) void qr_td_kernel(
   const int a_star = xa_qr::greedy((theta_next_o ? theta_next_o : theta_next_t) + row, A, N,
                                    lane, nullptr);
   const float* tq = theta_next_t + row + (size_t)a_star * N;
-  const float d = done[b], r = rew[b];
-  for (int j = lane; j < N; j += kLanes) ys[j] = xa_qr::target(tq[j], d, gamma, r);
+  const float d = done[b], r = rew[b], g = xa_td::discount_of(gamma, discounts, b);
+  for (int j = lane; j < N; j += kLanes) ys[j] = xa_qr::target(tq[j], d, g, r);
   wave_sync();
 
   const int ab = act[b];
@@ -138,12 +138,13 @@ extern "C" int xa_qr_act(const float* theta, int n, int n_actions, int n_quantil
   return 0;
 }
 
-extern "C" int xa_qr_td_grad(const float* theta, const float* theta_next_target,
-                             const float* theta_next_online, const int* actions,
-                             const float* rewards, const float* dones, int batch, int n_actions,
-                             int n_quantiles, float gamma, float huber_kappa, float* dtheta,
-                             float* loss, int* adam_step, const float* is_weights,
-                             float* td_abs, void* stream) {
+extern "C" int xa_qr_td_grad_n(const float* theta, const float* theta_next_target,
+                               const float* theta_next_online, const int* actions,
+                               const float* rewards, const float* dones, int batch,
+                               int n_actions, int n_quantiles, float gamma, float huber_kappa,
+                               float* dtheta, float* loss, int* adam_step,
+                               const float* is_weights, float* td_abs, const float* discounts,
+                               void* stream) {
   XA_CHECK_ARG(theta && theta_next_target && actions && rewards && dones && dtheta,
                "xa_qr_td_grad: bad arguments");
   XA_CHECK_ARG(shape_ok(batch, n_actions, n_quantiles),
@@ -153,7 +154,18 @@ extern "C" int xa_qr_td_grad(const float* theta, const float* theta_next_target,
   hipLaunchKernelGGL(qr_td_kernel, dim3(row_blocks(batch)), dim3(kBlock), 0,
                      (hipStream_t)stream, theta, theta_next_target, theta_next_online, actions,
                      rewards, dones, batch, n_actions, n_quantiles, gamma, huber_kappa, dtheta,
-                     loss, adam_step, is_weights, td_abs);
+                     loss, adam_step, is_weights, td_abs, discounts);
   XA_CHECK_LAUNCH("xa_qr_td_grad");
   return 0;
+}
+
+extern "C" int xa_qr_td_grad(const float* theta, const float* theta_next_target,
+                             const float* theta_next_online, const int* actions,
+                             const float* rewards, const float* dones, int batch, int n_actions,
+                             int n_quantiles, float gamma, float huber_kappa, float* dtheta,
+                             float* loss, int* adam_step, const float* is_weights,
+                             float* td_abs, void* stream) {
+  return xa_qr_td_grad_n(theta, theta_next_target, theta_next_online, actions, rewards, dones,
+                         batch, n_actions, n_quantiles, gamma, huber_kappa, dtheta, loss,
+                         adam_step, is_weights, td_abs, nullptr, stream);
 }

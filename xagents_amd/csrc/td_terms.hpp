@@ -64,6 +64,12 @@ XA_DEV float weighted(float x, const float* is_weights, int b) {
 }
 XA_DEV float td_abs_of(float e) { return fabsf(e); }
 
+// n-step replay (nstep_terms.hpp): the discount dqn_target receives is the sample's own
+// gamma^m where the batch carries one, else gamma (no discounts: the one-step bits).
+XA_DEV float discount_of(float gamma, const float* discounts, int b) {
+  return discounts ? discounts[b] : gamma;
+}
+
 // standard normal from Philox4x32-10 (Box-Muller on two 24-bit uniforms, u1 in (0, 1])
 XA_DEV float philox_normal(uint32_t i, uint32_t j, uint64_t ctr, uint64_t seed) {
   const xa_u4 r = xa_philox(i, j, (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed,

@@ -16,6 +16,10 @@ train_step (dqn/agent.py:182-197), all on device except the reference's host RNG
 at_step_end: hard target copy when steps % target_sync_steps == 0 (xa_polyak, tau 1).
 
 prioritized=True (per.py; NOT a parity mode): the sampler is the phase's slot source (base.py).
+n_steps > 1 (csrc/nstep_terms.hpp; NOT a parity mode, the reference trains its replay agents on
+one-step targets): the gather is xa_ring_gather_nstep -- each sampled slot's walk over up to
+n_steps ring entries, folded into one transition and its gamma^m (self.b_disc) -- and the TD
+head xa_dqn_td_grad_n with those discounts. ReplayBuffer1 buffers only, n_steps <= 64.
 """
 import os
 
@@ -68,7 +72,37 @@ class DQN(OffPolicy):
         self.batch_dtypes = ['uint8', 'int64', 'float64', 'bool', 'uint8']
         self._setup_device()
 
+    def _check_nstep(self):
+        """n_steps > 1 (multi-step targets, csrc/nstep_terms.hpp) needs rings whose consecutive
+        slots are consecutive transitions, and a walk one wave owns."""
+        from xagents_amd.utils.buffers import ReplayBuffer2
+        n, b0 = self.n_steps, self.buffers[0]
+        if n == 1:
+            return
+        if n != int(n) or n < 1:
+            raise ValueError(f'n_steps must be a positive integer, got {n}')
+        if isinstance(b0, ReplayBuffer2):
+            raise ValueError(
+                'n_steps > 1 needs ReplayBuffer1 buffers: ReplayBuffer2 overwrites row 0 once '
+                'the ring is full, so neighbouring slots are not consecutive transitions')
+        if n > 64 or n > b0.size:
+            raise ValueError(f'n_steps must be at most min(64, buffer size {b0.size}), got {n}')
+
+    def _nstep(self):
+        """DeviceReplay.gather's n-step argument, or None for one-step targets."""
+        if self.n_steps == 1:
+            return None
+        return int(self.n_steps), float(np.float32(self.gamma)), self.b_disc
+
+    def _td_entry(self, one_step, n_step):
+        """(the TD head's entry point, its trailing arguments): `one_step` as ever, or with
+        n_steps > 1 its per-sample-discount form `n_step` and the batch's discounts."""
+        if self.n_steps == 1:
+            return one_step, ()
+        return n_step, (self.b_disc.data_ptr(),)
+
     def _setup_device(self):
+        self._check_nstep()
         self._setup_offpolicy((), np.int32)
         self._learn_captured = CapturedPhase()
         k = self.replay.k
@@ -84,6 +118,8 @@ class DQN(OffPolicy):
         self.b_act = torch.zeros(B, dtype=torch.int32, device=dev)
         self.b_rew = torch.zeros(B, dtype=torch.float32, device=dev)
         self.b_done = torch.zeros(B, dtype=torch.float32, device=dev)
+        if self.n_steps > 1:  # each sample's gamma^m (xa_ring_gather_nstep)
+            self.b_disc = torch.zeros(B, dtype=torch.float32, device=dev)
         self.dq = torch.zeros(B, self.n_actions, dtype=torch.float32, device=dev)
         self.td_loss = torch.zeros(B, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.model.n_params, dtype=torch.float32, device=dev)
@@ -188,7 +224,7 @@ class DQN(OffPolicy):
         self._draw_slots()
         B = self.batch_size
         self.replay.gather(self._phase_slots(), self.xb[:B], self.b_act, self.b_rew,
-                           self.b_done, self.xb[B:])
+                           self.b_done, self.xb[B:], self._nstep())
         return [self.xb[:B], self.b_act, self.b_rew, self.b_done, self.xb[B:]]
 
     def _td_grad(self):
@@ -196,18 +232,20 @@ class DQN(OffPolicy):
         Adam reads it after the backward)."""
         B = self.batch_size
         q_all = self.ex_online.forward(self.xb if self.double else self.xb[:B])[0]
-        if self._head_fused() and self.per is None:
+        if self._head_fused() and self.per is None and self.n_steps == 1:
             # the TD target and its gradient ride in the target head's launch (mode 1)
             self.ex_target.forward(self.xb[B:], head=self._head_args('td'))
             return
         q_next_t = self.ex_target.forward(self.xb[B:])[0]
         q_next_o = q_all[B:].data_ptr() if self.double else None
-        # (the fused head carries no weights; null weights: xa_dqn_td_grad's bytes)
-        call('xa_dqn_td_grad_w', q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
+        # (the fused head carries neither weights nor discounts; null weights:
+        # xa_dqn_td_grad's bytes)
+        name, disc = self._td_entry('xa_dqn_td_grad_w', 'xa_dqn_td_grad_n')
+        call(name, q_all.data_ptr(), q_next_t.data_ptr(), q_next_o,
              self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
              self.n_actions, kernels._f32(self.gamma), kernels._f32(self.huber_delta or 0.0),
              self.dq.data_ptr(), self.td_loss.data_ptr(),
-             self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), stream())
+             self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), *disc, stream())
 
     # the raw gradient of the dense layers whose Adam step runs inside their weight-gradient
     # GEMM is written to self.grad only on request (the raw-gradient parity tests)
@@ -318,8 +356,16 @@ class DQN(OffPolicy):
         hooks = ('get_targets', 'update_gradients', 'concat_buffer_samples', 'get_actions')
         return any(getattr(type(self), h) is not getattr(base, h) for h in hooks)
 
+    def _refuse_composed_nstep(self):
+        if self.n_steps > 1:
+            raise NotImplementedError(
+                f'{type(self).__name__} overrides a reference hook, and the hooks\' signatures '
+                f'(get_targets(states, actions, rewards, dones, new_states)) carry no per-sample '
+                f'discounts: n_steps > 1 runs on the device step only')
+
     def _composed_step(self):
         """The train step through the hooks, each calling the library."""
+        self._refuse_composed_nstep()
         actions = self.get_actions()
         self._env_step(actions.to(torch.int32).contiguous())
         self.steps += self.n_envs
@@ -367,7 +413,7 @@ class DQN(OffPolicy):
         B = self.batch_size
         stage = self._gather_stage()
         self.replay.gather(self._phase_slots(stage), self.xb[:B], self.b_act, self.b_rew,
-                           self.b_done, self.xb[B:])
+                           self.b_done, self.xb[B:], self._nstep())
         if stage is not None and self._stage_early() and \
                 not torch.cuda.is_current_stream_capturing():
             # the gather is the staged slots' only reader: the next step's put waits for it

@@ -10,7 +10,8 @@ two head launches differ:
                          batch-mean loss                                     -> xa_qr_td_grad
 Everything else is DQN's: the rings and the slot staging, the layer executor's backward with
 its fused Adam, the captured learner phase, the target sync, prioritized replay (the priority
-is the TD error of the means, so per_eps keeps DQN's units).
+is the TD error of the means, so per_eps keeps DQN's units), n-step targets (n_steps > 1:
+DQN's gather, and xa_qr_td_grad_n takes each sample's gamma^m).
 """
 import numpy as np
 import torch
@@ -105,11 +106,12 @@ class QRDQN(DQN):
         th_all = self.ex_online.forward(self.xb if self.double else self.xb[:B])[0]
         th_next_t = self.ex_target.forward(self.xb[B:])[0]
         th_next_o = th_all[B:].data_ptr() if self.double else None
-        call('xa_qr_td_grad', th_all.data_ptr(), th_next_t.data_ptr(), th_next_o,
+        name, disc = self._td_entry('xa_qr_td_grad', 'xa_qr_td_grad_n')
+        call(name, th_all.data_ptr(), th_next_t.data_ptr(), th_next_o,
              self.b_act.data_ptr(), self.b_rew.data_ptr(), self.b_done.data_ptr(), B,
              self.n_actions, self.n_quantiles, kernels._f32(self.gamma),
              kernels._f32(self.huber_kappa), self.dq.data_ptr(), self.td_loss.data_ptr(),
-             self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), stream())
+             self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), *disc, stream())
 
     # ---- composed path (a subclass that overrides a hook) ----------------------------
     def _quantiles(self, states, model):
@@ -156,6 +158,7 @@ class QRDQN(DQN):
 
     def _composed_step(self):
         """DQN's, with the sampled actions handed to update_gradients."""
+        self._refuse_composed_nstep()
         actions = self.get_actions()
         self._env_step(actions.to(torch.int32).contiguous())
         self.steps += self.n_envs

@@ -23,8 +23,8 @@ import random
 import numpy as np
 import torch
 
-from xagents_amd._lib import (XA_RING_DEQUE, XA_RING_RB2, XaGatherArgs, call, mapped_pinned,
-                              stream)
+from xagents_amd._lib import (XA_RING_DEQUE, XA_RING_RB2, XaGatherArgs, XaNstepGatherArgs, call,
+                              mapped_pinned, stream)
 from xagents_amd.utils.buffers import ReplayBuffer1, ReplayBuffer2
 
 
@@ -238,13 +238,34 @@ class DeviceReplay:
         st.consumed(i)
         return self.slots
 
-    def gather(self, slots, states, actions, rewards, dones, new_states):
+    def gather(self, slots, states, actions, rewards, dones, new_states, nstep=None):
         """The five fields of one sampled batch in one xa_ring_gather_fields launch (the
         argument block is built once per destination set and reused). slots: the device
-        address of n * k int64 slots (self.slots', a SlotStage buffer's, the sampler's)."""
+        address of n * k int64 slots (self.slots', a SlotStage buffer's, the sampler's).
+        nstep = (n_steps, gamma as f32, discounts [n * k] f32): the n-step transition of each
+        slot and its gamma^m instead, in one xa_ring_gather_nstep launch (deque rings)."""
         sp, sn = slots, self.n * self.k
         key = (sp, sn, states.data_ptr(), actions.data_ptr(),
                rewards.data_ptr(), dones.data_ptr(), new_states.data_ptr())
+        if nstep is not None:
+            n_steps, gamma, discounts = nstep
+            key += (n_steps, gamma, discounts.data_ptr())
+            if getattr(self, '_gkey', None) != key:
+                a = XaNstepGatherArgs()
+                a.ring_states, a.ring_new_states = self.states.data_ptr(), self.new_states.data_ptr()
+                a.ring_actions = self.actions.data_ptr()
+                a.ring_rewards, a.ring_dones = self.rewards.data_ptr(), self.dones.data_ptr()
+                a.ring_count = self.count.data_ptr()
+                a.obs_bytes, a.act_bytes, a.capacity = self.obs_bytes, self.act_bytes, self.cap
+                a.ring_kind, a.n_steps, a.n_items, a.gamma = self.kind, n_steps, sn, gamma
+                a.slots = sp
+                a.states, a.actions, a.new_states = \
+                    states.data_ptr(), actions.data_ptr(), new_states.data_ptr()
+                a.rewards, a.dones = rewards.data_ptr(), dones.data_ptr()
+                a.discounts = discounts.data_ptr()
+                self._gargs, self._gkey = a, key
+            call('xa_ring_gather_nstep', ctypes.byref(self._gargs), stream())
+            return
         if getattr(self, '_gkey', None) != key:
             a = XaGatherArgs()
             fields = ((self.states, states, self.obs_bytes),
