@@ -678,6 +678,47 @@ int xa_qr_td_grad_n(const float* theta, const float* theta_next_target,
                     const float* is_weights, float* td_abs, const float* discounts,
                     void* stream);
 
+/* Categorical DQN (C51; Bellemare et al., https://arxiv.org/abs/1707.06887; csrc/c51.hip,
+ * csrc/c51_terms.hpp states the arithmetic). A network output row is [n_actions][n_atoms]
+ * logits, action-major: output a K + i is atom i of action a, at z_i = v_min + i delta,
+ * delta = (v_max - v_min) / (K - 1). p(a) = softmax of action a's K logits and
+ * Q[a] = sum_i p_i(a) z_i. One wave per row; 2 <= n_atoms <= 256, any n_actions >= 1, v_min and
+ * v_max finite with v_max > v_min; anything else is an error before anything is launched.
+ *
+ * xa_c51_act: actions[r] = first argmax_a Q[a] of row r of logits [n][A K], or
+ * random_actions[r] when use_random (xa_dqn_act's rule; logits and q_out are then not
+ * touched). q_out [n][A] (optional) receives the expected Q values.
+ *
+ * xa_c51_project (Algorithm 1 as a gather): a* = argmax_a Q[a] of logits_next_target's row
+ * (of logits_next_online's when it is not NULL: double Q), p' = softmax of
+ * logits_next_target[b][a*], Tz_j = clip(z_j g + r, v_min, v_max) (z_j counts as 0 where
+ * done), g = discounts[b] (optional: each sample's gamma^m of n-step replay) or gamma,
+ * b_j = (Tz_j - v_min) / delta, and target_dist[b][i] = sum_j p'_j max(0, 1 - |b_j - i|),
+ * j ascending: no atomics, a fixed order, and the whole mass on atom i where b_j == i.
+ *
+ * xa_c51_td_grad: the fused head. m = xa_c51_project's row (the same device code), or
+ * target_dist[b] when target_dist is not NULL (logits_next_*, rewards, dones, discounts are
+ * then not read and may be NULL). With p = softmax of logits[b][a_b]:
+ * loss[b] (optional) = -sum_i m_i log p_i, and the gradient of the batch MEAN
+ * dlogits[b][a_b][i] = (p_i - m_i) / batch, 0 at every other action's outputs: the whole
+ * [batch][A K] array is written. adam_step (optional) is bumped by one in the same launch.
+ * Prioritized replay, both optional and both NULL the unweighted bytes: is_weights [batch]
+ * (in) multiplies dlogits' row and loss[b] by w_b, one f32 multiply after the unweighted
+ * value; td_abs [batch] (out) = |sum_i m_i z_i - Q[a_b]|, the TD error of the means. */
+int xa_c51_act(const float* logits, int n, int n_actions, int n_atoms, float v_min, float v_max,
+               const int* random_actions, int use_random, int* actions, float* q_out,
+               void* stream);
+int xa_c51_project(const float* logits_next_target, const float* logits_next_online,
+                   const float* rewards, const float* dones, const float* discounts, int batch,
+                   int n_actions, int n_atoms, float v_min, float v_max, float gamma,
+                   float* target_dist, void* stream);
+int xa_c51_td_grad(const float* logits, const float* logits_next_target,
+                   const float* logits_next_online, const float* target_dist,
+                   const int* actions, const float* rewards, const float* dones, int batch,
+                   int n_actions, int n_atoms, float v_min, float v_max, float gamma,
+                   float* dlogits, float* loss, int* adam_step, const float* is_weights,
+                   float* td_abs, const float* discounts, void* stream);
+
 /* The Q head (the last dense layer, N <= 8 actions: xa_gemm's row-dot shape) with DQN's
  * per-row step fused into the same launch. mode 0: actions[m] = first argmax of row m
  * (xa_dqn_act's greedy branch); mode 1: the head is the TARGET network's over s', and row b

@@ -18,13 +18,6 @@ using xa_qr::kOwned;
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kLanes;  // rows per workgroup
 
-// the wave's LDS stores are visible to its own lanes' loads behind this
-XA_DEV void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // actions[r] = first argmax of the row's mean Q, or the host-drawn action (xa_dqn_act's rule)
 __global__ __launch_bounds__(kBlock) void qr_act_kernel(const float* __restrict__ theta, int n,
                                                         int A, int N,
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void qr_td_kernel(
   const float* tq = theta_next_t + row + (size_t)a_star * N;
   const float d = done[b], r = rew[b], g = xa_td::discount_of(gamma, discounts, b);
   for (int j = lane; j < N; j += kLanes) ys[j] = xa_qr::target(tq[j], d, g, r);
-  wave_sync();
+  xa_wave_sync();
 
   const int ab = act[b];
   const float* th = theta + row + (size_t)ab * N;

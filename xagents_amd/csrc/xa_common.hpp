@@ -274,6 +274,14 @@ XA_DEV float xa_sum8(float v) {
   return v + XA_DPP_F(v, 0x141);
 }
 
+// a wave's LDS stores are visible to its own lanes' loads behind this (the one-wave-per-row
+// kernels of qr.hip / c51.hip: no workgroup barrier, a wave past the batch has left)
+XA_DEV void xa_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ----------------------------------------------------------------------------
 // Feistel pseudo-random permutation on [0, n) (cycle walking), used for the
 // device-side minibatch shuffle that replaces tf.random.shuffle

@@ -18,11 +18,11 @@ import torch
 
 from xagents_amd import kernels
 from xagents_amd._lib import call, stream
-from xagents_amd.dqn.agent import DQN
+from xagents_amd.dqn.wide import WideHeadDQN
 from xagents_amd.layers import LayerExecutor
 
 
-class QRDQN(DQN):
+class QRDQN(WideHeadDQN):
     """Distributional Reinforcement Learning with Quantile Regression
     https://arxiv.org/abs/1710.10044
 
@@ -31,7 +31,7 @@ class QRDQN(DQN):
     loss's threshold (the discontinuous pinball loss, kappa = 0, has no path here).
     double / prioritized and DQN's other arguments keep their meaning; huber_delta has none."""
 
-    _supports_prioritized = True
+    _width_arg, _agent_id = 'n_quantiles', 'qrdqn'
 
     def __init__(self, envs, model, buffers, n_quantiles=32, huber_kappa=1.0, **kwargs):
         if 'huber_delta' in kwargs:
@@ -45,58 +45,11 @@ class QRDQN(DQN):
         self.huber_kappa = float(huber_kappa)
         super(QRDQN, self).__init__(envs, model, buffers, **kwargs)
 
-    def _setup_device(self):
-        width = self.n_actions * self.n_quantiles
-        outs = list(self.model.outputs)
-        units = [self.model.layers[i].units for i in outs]
-        assert units == [width], (
-            f'QRDQN needs a model with one output of n_actions * n_quantiles = '
-            f'{self.n_actions} * {self.n_quantiles} = {width} units, got {units} '
-            f'(create_model(..., \'qrdqn\', ..., n_quantiles={self.n_quantiles}))')
-        super(QRDQN, self)._setup_device()
-        dev = self.device
-        self.dq = torch.zeros(self.batch_size, width, dtype=torch.float32, device=dev)
-        self.q_mean = torch.zeros(self.n_envs, self.n_actions, dtype=torch.float32, device=dev)
-
-    def _head_fused(self):
-        """Never: xa_dqn_head is the scalar-Q head on a row-dot layer of <= 8 outputs."""
-        return False
-
-    # ---- acting --------------------------------------------------------------------
-    def _qr_act(self, theta, n, actions, q_mean=None, random_actions=None):
+    def _act(self, theta, n, actions, q=None, random_actions=None):
         call('xa_qr_act', None if theta is None else theta.data_ptr(), n, self.n_actions,
              self.n_quantiles, None if random_actions is None else random_actions.data_ptr(),
              int(random_actions is not None), actions.data_ptr(),
-             None if q_mean is None else q_mean.data_ptr(), stream())
-
-    def get_model_outputs(self, inputs, models, training=True):
-        """[argmax of the mean Q, mean Q [n, A]] for a device batch of states."""
-        model = models[0] if isinstance(models, (list, tuple)) else models
-        x = torch.as_tensor(inputs, device=self.device).contiguous()
-        n = x.shape[0]
-        theta = LayerExecutor(model, n).forward(x)[0]
-        act = torch.empty(n, dtype=torch.int32, device=self.device)
-        q = torch.empty(n, self.n_actions, dtype=torch.float32, device=self.device)
-        self._qr_act(theta, n, act, q)
-        return act, q
-
-    def get_actions(self):
-        """Epsilon-greedy on the mean Q, the host draws DQN's (all envs random or all
-        greedy)."""
-        if np.random.random() < self.epsilon:
-            r = np.random.randint(0, self.n_actions, self.n_envs)
-            self._rand_actions.copy_(torch.from_numpy(r.astype(np.int32)))
-            self._qr_act(None, self.n_envs, self.actions, random_actions=self._rand_actions)
-        else:
-            self._play_actions()
-        return self.actions
-
-    def _play_actions(self):
-        """play(): the greedy action of the mean Q for every env (the means at
-        self.q_mean)."""
-        theta = self.ex_act.forward(self.envs.state)[0]
-        self._qr_act(theta, self.n_envs, self.actions, self.q_mean)
-        return self.actions
+             None if q is None else q.data_ptr(), stream())
 
     # ---- learner phase -------------------------------------------------------------
     def _td_grad(self):
@@ -114,15 +67,11 @@ class QRDQN(DQN):
              self.model.optimizer.iterations.data_ptr(), *self._per_ptrs(), *disc, stream())
 
     # ---- composed path (a subclass that overrides a hook) ----------------------------
-    def _quantiles(self, states, model):
-        x = torch.as_tensor(states, device=self.device).contiguous()
-        return LayerExecutor(model, x.shape[0]).forward(x)[0].clone()
-
     def get_targets(self, states, actions, rewards, dones, new_states):
         """Target quantiles y [B, N]: theta_target(s')[a*] gamma + r, r where done, a* the
         greedy action of the target net's mean Q on s' (the online net's when double)."""
         B, N = new_states.shape[0], self.n_quantiles
-        th_t = self._quantiles(new_states, self.target_model).view(B, self.n_actions, N)
+        th_t = self._outputs(new_states, self.target_model).view(B, self.n_actions, N)
         a_next = self.get_model_outputs(
             new_states, self.model if self.double else self.target_model)[0].long()
         v = th_t[torch.arange(B, device=self.device), a_next]
@@ -151,19 +100,7 @@ class QRDQN(DQN):
              zeros.data_ptr(), zeros.data_ptr(), B, A, N, kernels._f32(1.0),
              kernels._f32(self.huber_kappa), dq.data_ptr(), None, opt.iterations.data_ptr(),
              None, None, stream())
-        ex.backward([dq], self.grad)
-        kernels.clip_adam(self.model.theta, opt.m, opt.v, self.grad, opt.iterations,
-                          opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon,
-                          clip_norm=0.0, workspace=self.adam_ws)
-
-    def _composed_step(self):
-        """DQN's, with the sampled actions handed to update_gradients."""
-        self._refuse_composed_nstep()
-        actions = self.get_actions()
-        self._env_step(actions.to(torch.int32).contiguous())
-        self.steps += self.n_envs
-        batch = self.concat_buffer_samples()
-        self.update_gradients(batch[0], self.get_targets(*batch), batch[1])
+        self._composed_apply(ex, dq)
 
     def train_step(self):
         if self._hooks_overridden(QRDQN):
